@@ -34,8 +34,8 @@ test-cov: build
 bench: build  ## headline benchmark, 1 GPU
 	$(PY) bench.py
 
-bench-node: build  ## the node: bench.py launches its ranks itself
-	$(PY) bench.py --gpus $(GPUS)
+bench-node: build  ## the node: bench.py launches its ranks itself; --full: spread check + config-3 pass too
+	$(PY) bench.py --gpus $(GPUS) --full
 
 api-reference:  ## re-export api_reference/openapi.json from the conformance app
 	$(PY) -c "import json; from quorum_amd.server.app import create_app; from quorum_amd.utils.config import load_config; \

@@ -15,6 +15,10 @@ A *step* = ``--batch`` completed client requests per rank.  W warmup steps, then
 K timed steps bracketed by barrier + ``torch.cuda.synchronize()``; the slowest rank's
 time is used; rank 0 prints one JSON line.  ``value`` = total completed requests / time
 (whole node).  Weak scaling: per-rank load is fixed as N grows.
+
+A plain run does only that.  ``--full`` adds, after the timed steps, the harness ceiling and, at
+N > 1, the spread check and the config-3 pass; ``--dump-outputs DIR`` writes what the servers
+of the timed steps answer to the same requests right after them as ``.npy`` arrays (dump_outputs).
 """
 from __future__ import annotations
 
@@ -96,7 +100,7 @@ SCENARIOS = {
                        desc="1 mock backend, non-streaming concatenate (passthrough), CPU engine"),
     # the harness alone: the load generator straight against one mock backend, no proxy, same
     # validation (every content byte of the mock's stream) — SURVEY §6 row 1 / §7.4 item 4.
-    # Every other scenario also measures this after its timed region (harness_ceiling).
+    # With --full every other scenario also measures this after its timed region (harness_ceiling).
     "direct": dict(n=1, strategy="concatenate", hide_final=False, skip=True, faults={}, timeout=30, direct=True,
                    batch=131072, baseline=319.0, baseline_ttft_ms=18.9, baseline_source="direct mock backend under the "
                    "survey's Python harness (SURVEY §6 row 1: the harness ceiling there)",
@@ -407,6 +411,79 @@ def loadgen(bin_dir, port, conns, requests, threads, timeout, expect=None, path=
     if out.stderr.strip():
         print(out.stderr.strip()[-3000:], file=sys.stderr, flush=True)  # the first invalid responses
     return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: all arrays of one rank together
+
+
+def response_texts(body: bytes, stream: bool) -> dict:
+    """What a client holds after one response, by source: every event id's concatenated delta
+    content (``chatcmpl-parallel-<i>``: backend i's stream, ``chatcmpl-parallel-final``: the final
+    event), or the message of a non-streaming completion — UTF-8 bytes.  The event boundaries,
+    the interleaving of the backends' events and ``created`` depend on timing and are left out;
+    these texts depend on the inputs alone."""
+    if not stream:
+        msg = json.loads(body)["choices"][0]["message"]["content"]
+        return {"message": (msg or "").encode()}
+    texts = {}
+    for seg in body.split(b"\n\n"):
+        if not seg.startswith(b"data: ") or seg[6:] == b"[DONE]":
+            continue
+        ev = json.loads(seg[6:])
+        for ch in ev.get("choices") or []:
+            c = (ch.get("delta") or {}).get("content")
+            if c:
+                texts[ev.get("id", "")] = texts.get(ev.get("id", ""), b"") + c.encode()
+    return texts
+
+
+def fetch_responses(port: int, path: str, stream: bool, n: int) -> list:
+    """``n`` requests, byte for byte the load generator's, one after the other on one keep-alive
+    connection to the servers the timed steps ran against: [(status, body)]."""
+    import http.client
+
+    body = ('{"model": "bench", "messages": [{"role": "user", "content": "Hello!"}], "stream": '
+            + ("true" if stream else "false") + "}")
+    out = []
+    c = http.client.HTTPConnection("127.0.0.1", port, timeout=60)
+    try:
+        for _ in range(n):
+            c.request("POST", path, body=body, headers={"content-type": "application/json",
+                                                        "authorization": "Bearer bench"})
+            r = c.getresponse()
+            out.append((r.status, r.read()))
+    finally:
+        c.close()
+    return out
+
+
+def dump_outputs(out_dir: str, responses: list, stream: bool, rank: int) -> dict:
+    """--dump-outputs: ``responses`` (fetch_responses: what a client of the timed path receives,
+    taken right after the timed steps from the same, still running servers) as float32 arrays,
+    one row per response: ``status.npy`` (HTTP status) and ``content_<source>.npy``
+    (response_texts: the UTF-8 bytes of each source's text, rows padded with -1).  Rank r > 0
+    writes ``<name>_rank<r>.npy``.  Rows are dropped from the end to keep a rank's arrays within
+    DUMP_CAP_BYTES."""
+    import re
+
+    import numpy as np
+
+    rows = [(status, response_texts(body, stream) if status == 200 else {}) for status, body in responses]
+    names = sorted({k for _, t in rows for k in t})
+    width = {k: max(len(t.get(k, b"")) for _, t in rows) for k in names}
+    rows = rows[:DUMP_CAP_BYTES // (4 * (1 + sum(width.values())))]
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    arrays = {"status": np.array([s for s, _ in rows], dtype=np.float32)}
+    for k in names:
+        a = np.full((len(rows), width[k]), -1.0, dtype=np.float32)
+        for i, (_, t) in enumerate(rows):
+            b = t.get(k, b"")
+            a[i, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+        arrays["content_" + re.sub(r"[^A-Za-z0-9]+", "_", k).strip("_")] = a
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}{sfx}.npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def wait_port(host: str, port: int, timeout: float) -> bool:
@@ -1110,6 +1187,24 @@ def wait_ready(procs, timeout: float) -> bool:
     return False
 
 
+def built_tools() -> list:
+    """Build the extension and the C++ tools if they are stale (after `make build`: a check of
+    the build keys, under the build's lock) and return the tools' paths.  In a tree this user
+    may not write to (built by another user) the lock cannot be taken: what was built there
+    runs, and a missing extension or tool is an error."""
+    from quorum_amd.ops import build as qbuild
+
+    try:
+        qbuild.build()
+        return qbuild.build_tools()
+    except PermissionError:
+        tools = [qbuild.BIN / name for name in qbuild.TOOLS]
+        missing = [str(p) for p in [qbuild.ext_path()] + tools if not p.exists()]
+        if missing:
+            raise RuntimeError(f"read-only tree and not built: {missing}") from None
+        return tools
+
+
 def main() -> int:
     # the bench measures the GPU path itself: serve's latency mode (idle loops' streams on the
     # HIP engine's host path) stays off unless asked for (QMX_LIGHT_HOST=N)
@@ -1147,13 +1242,21 @@ def main() -> int:
     ap.add_argument("--port", type=int, default=int(os.environ.get("QMX_BENCH_PORT", "18000")))
     ap.add_argument("--timeout", type=float, default=900)
     ap.add_argument("--scenario", default="headline", choices=sorted(SCENARIOS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the harness "
+                         "ceiling (--ceiling) and, at N > 1, the spread check (--spread-check) and the config-3 "
+                         "pass; a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what a client of the timed path receives — one more response "
+                         "per connection from the same running servers, per source text — as DIR/<name>.npy "
+                         "(float32)")
     ap.add_argument("--spread-check", type=int, default=1,
-                    help="N > 1: after the timed steps, validate spread placement (RCCL finals) end to end")
+                    help="--full, N > 1: after the timed steps, validate spread placement (RCCL finals) end to end")
     ap.add_argument("--placement", default="local", choices=["local", "spread"],
                     help="spread: a session's backend streams run on consecutive ranks (RCCL exchange)")
     ap.add_argument("--ceiling", type=float, default=2.0,
-                    help="seconds of the harness-ceiling check after the timed region (the load generator straight "
-                         "against one mock, no proxy: harness_ceiling_req_s); 0 skips it")
+                    help="--full: seconds of the harness-ceiling check after the timed region (the load generator "
+                         "straight against one mock, no proxy: harness_ceiling_req_s); 0 skips it")
     ap.add_argument("--plan", action="store_true",
                     help="print the per-rank thread / CPU plan for --gpus N on this node (QMX_SYSFS_ROOT: a "
                          "copy of /sys; QMX_BENCH_QUOTA: the CPU quota) and exit — nothing is launched or bound")
@@ -1232,10 +1335,7 @@ def main() -> int:
     direct = bool(sc.get("direct"))
     stream = bool(sc.get("stream", True))
 
-    from quorum_amd.ops import build as qbuild
-
-    qbuild.build()
-    bin_dir = os.path.dirname(str(qbuild.build_tools()[0]))
+    bin_dir = os.path.dirname(str(built_tools()[0]))
     from quorum_amd.parallel.exchange import exchange_env
     from quorum_amd.parallel.topology import summary as link_summary
     from quorum_amd.serve import spawn_workers, wait_healthy
@@ -1384,11 +1484,15 @@ def main() -> int:
             bad += int(bd["exchange"]["delta_mismatch"] + bd["exchange"]["worker_nodata"])
         # the harness alone, right after the timed region: the same load generator (connections,
         # threads, validation) straight against this rank's first mock backend, no proxy
+        dumped = None
+        if args.dump_outputs and not dead:  # one response per client connection of the timed steps
+            dumped = dump_outputs(args.dump_outputs, fetch_responses(proxy_port, path, stream, args.conns), stream, rank)
+        # --full only, below: measurements and checks of their own, which the headline does not need
         ceiling = None
-        if args.ceiling > 0 and not direct and not dead:
+        if args.full and args.ceiling > 0 and not direct and not dead:
             ceiling = harness_ceiling(bin_dir, mock_ports[0], args, mock_procs[0], tmp)
         spread = c3_rows = None
-        if (dist is not None and world > 1 and args.spread_check and args.impl == "native"
+        if (args.full and dist is not None and world > 1 and args.spread_check and args.impl == "native"
                 and args.placement == "local" and not direct):
             _kill(proxy_procs)  # done measuring; the check brings up its own proxy set
             spread = spread_check(args, SCENARIOS["headline"], rank, world, engine, device, bin_dir, tmp,
@@ -1506,6 +1610,8 @@ def main() -> int:
                 res["harness_ceiling"] = dict(cr[0], ranks=len(cr)) if len(cr) == 1 else {"per_rank": cr}
             if world > 1:  # every rank's own proxy: distinct pids, its own counters
                 res["breakdown_per_rank"] = [compact_breakdown(r, b, row) for r, (b, row) in enumerate(zip(bd_rows, rows))]
+            if dumped is not None:  # --dump-outputs: rank 0's arrays (name -> shape)
+                res["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
             if dead or dead_warm:
                 res["exited"] = dead or dead_warm
             if spread is not None:  # outside the timed region; per rank, each from its own proxy

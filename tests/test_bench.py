@@ -70,13 +70,102 @@ def test_bench_single_rank_foreign_cwd(tmp_path):
     assert res["config"]["global_batch"] == 128
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run measures the headline only (no harness ceiling: that is --full's), and
+    ``--dump-outputs DIR`` writes what a client of the timed path receives, taken right after
+    the timed steps — one row per connection, each backend's text as the mock streams it
+    outside its think block — the same arrays from run to run."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("qmx_bench_mod3", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "64",
+                            "--threads", "2", "--conns", "8", "--port", str(_free_port()), "--dump-outputs", str(out)],
+                           cwd=str(tmp_path), env=_env(), capture_output=True, text=True, timeout=240)
+        assert r.returncode == 0, r.stderr[-3000:]
+        res = _check(_json_lines(r.stdout)[0], 1, 3, 1)
+        assert res["valid"] is True and res["validated"] == 3 * 64
+        assert "harness_ceiling" not in res and "harness_ceiling_req_s" not in res
+        arrays = {p.name: np.load(p) for p in sorted(out.iterdir())}
+        assert {n: list(a.shape) for n, a in arrays.items()} == {k + ".npy": v for k, v in
+                                                                 res["dumped_outputs"]["arrays"].items()}
+        runs.append(arrays)
+    a, b = runs
+    assert sorted(a) == ["content_chatcmpl_parallel_0.npy", "content_chatcmpl_parallel_1.npy", "status.npy"]
+    want = np.frombuffer(bench.mock_expected(os.path.join(ROOT, "quorum_amd", "bin"))["stream_text"].encode(), np.uint8)
+    for name in a:
+        assert a[name].dtype == np.float32 and a[name].shape[0] == 8 and np.array_equal(a[name], b[name]), name
+    assert (a["status.npy"] == 200).all()
+    for i in range(2):
+        assert all(np.array_equal(row, want) for row in a[f"content_chatcmpl_parallel_{i}.npy"])
+
+
+def test_dump_outputs_rows_and_padding(tmp_path):
+    """bench.dump_outputs on synthetic responses: one row per response, each event id's delta
+    content concatenated (role, stop and [DONE] events carry none), shorter texts padded with
+    -1, and a response that is not a 200 as its status and no text."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("qmx_bench_mod4", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    def ev(eid, delta):
+        return b"data: " + json.dumps({"id": eid, "created": 1, "choices": [{"index": 0, "delta": delta}]}).encode() + b"\n\n"
+
+    responses = [(200, ev("chatcmpl-parallel", {"role": "assistant"}) + ev("chatcmpl-parallel-1", {"content": "\u00e9"})
+                  + ev("chatcmpl-parallel-0", {"content": "ab"}) + ev("chatcmpl-parallel-0", {"content": "c"})
+                  + ev("chatcmpl-parallel-0", {}) + b"data: [DONE]\n\n"),
+                 (200, ev("chatcmpl-parallel-0", {"content": "a"}) + b"data: [DONE]\n\n"),
+                 (503, b'{"error": {"message": "busy"}}')]
+    shapes = bench.dump_outputs(str(tmp_path / "out"), responses, True, 0)
+    assert shapes == {"status": [3], "content_chatcmpl_parallel_0": [3, 3], "content_chatcmpl_parallel_1": [3, 2]}
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in shapes}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["status"].tolist() == [200, 200, 503]
+    assert got["content_chatcmpl_parallel_0"].tolist() == [[97, 98, 99], [97, -1, -1], [-1, -1, -1]]
+    assert got["content_chatcmpl_parallel_1"].tolist() == [[0xC3, 0xA9], [-1, -1], [-1, -1]]
+    assert bench.dump_outputs(str(tmp_path / "r1"), responses[:2], True, 1)["status"] == [2]
+    assert sorted(p.name for p in (tmp_path / "r1").iterdir()) == [
+        "content_chatcmpl_parallel_0_rank1.npy", "content_chatcmpl_parallel_1_rank1.npy", "status_rank1.npy"]
+
+
+def test_bench_runs_what_was_built_in_a_tree_it_cannot_write(tmp_path, monkeypatch):
+    """A tree built by another user: the build lock cannot be taken (PermissionError), and the
+    bench runs the extension and tools that are there; a tree where one is missing is an
+    error, never a run without it."""
+    from quorum_amd.ops import build as qbuild
+
+    def denied(*a, **kw):
+        raise PermissionError(13, "Permission denied", str(qbuild.BUILD / ".lock"))
+
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("qmx_bench_mod5", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(qbuild, "build", denied)
+    assert bench.built_tools() == [qbuild.BIN / "qmx_mock", qbuild.BIN / "qmx_loadgen"]
+    monkeypatch.setattr(qbuild, "BIN", tmp_path)
+    with pytest.raises(RuntimeError, match="not built"):
+        bench.built_tools()
+
+
 @pytest.mark.slow
 def test_bench_two_ranks_torchrun(tmp_path):
     port = _free_port()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), BENCH,
                         "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "128", "--threads", "2",
-                        "--conns", "8", "--port", str(port)],
+                        "--conns", "8", "--port", str(port), "--full"],
                        cwd=str(tmp_path), env=_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = _json_lines(r.stdout)
@@ -97,7 +186,7 @@ def test_bench_two_ranks_spread_check_failure_is_agreed(tmp_path):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), BENCH,
                         "--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "64", "--threads", "2",
-                        "--conns", "8", "--port", str(port)],
+                        "--conns", "8", "--port", str(port), "--full"],
                        cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300)
     # the headline responses were fine: the run is valid, the failed spread check is reported
     # on its own (checks_ok false, a warning on stderr) instead of losing the measurement
@@ -120,7 +209,7 @@ def test_bench_gpus_flag_self_launches_ranks(tmp_path):
     env = dict(_env(), QMX_BENCH_NDEV="1")  # rehearsal: the ranks share (at most) one GPU
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--steps", "2", "--warmup", "1", "--batch", "128",
-                        "--threads", "2", "--conns", "8", "--port", str(port)],
+                        "--threads", "2", "--conns", "8", "--port", str(port), "--full"],
                        cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = _json_lines(r.stdout)
@@ -255,7 +344,7 @@ def test_bench_nonstream1_config1(tmp_path, impl):
     port = _free_port()
     r = subprocess.run([sys.executable, BENCH, "--scenario", "nonstream1", "--impl", impl, "--steps", "1",
                         "--warmup", "0", "--batch", "16" if impl == "reference" else "400", "--threads", "2",
-                        "--conns", "4", "--port", str(port), "--ceiling", "0.5"],
+                        "--conns", "4", "--port", str(port), "--full", "--ceiling", "0.5"],
                        cwd=str(tmp_path), env=_env(), capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads(_json_lines(r.stdout)[0])

@@ -93,15 +93,18 @@ def test_gpu_bench_light_host(tmp_path, conns, light, port):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, QMX_BENCH_ENGINE="hip", QMX_LIGHT_HOST=light)
+    # the engines' counters are snapshots up to 100 ms old: at 64 connections (some 400k req/s) the
+    # timed steps take several snapshots' time, or the breakdown's deltas could read 0
+    batch = 4096 if conns == 2 else 65536
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1",
-                        "--batch", "4096", "--conns", str(conns), "--port", str(port), "--ceiling", "0"],
+                        "--batch", str(batch), "--conns", str(conns), "--port", str(port), "--ceiling", "0"],
                        cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=180)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert lines, r.stderr[-3000:]
     res = json.loads(lines[-1])
     assert r.returncode == 0 and res["valid"] and res["invalid"] == 0, (res.get("invalid"), r.stderr[-2000:])
     bd = res["breakdown_one_rank"]
-    streams = 2 * (3 + 1) * 4096  # two backends per request, warmup included
+    streams = 2 * (3 + 1) * batch  # two backends per request, warmup included
     if light == "0":
         assert bd["light_host_opens"] == 0 and bd["kernel_launches"] > 0, bd
     elif conns == 2:
@@ -138,6 +141,49 @@ def test_gpu_bench_headline_valid(tmp_path, knob, port):
     res = json.loads(lines[-1])
     assert r.returncode == 0 and res["valid"] and res["invalid"] == 0, (res.get("invalid"), r.stderr[-2000:])
     assert res["validated"] == 4 * 8192 and res["breakdown_one_rank"]["kernel_launches"] > 0
+
+
+def test_gpu_bench_dump_outputs(tmp_path):
+    """``bench.py --dump-outputs`` on the HIP engine, final event on: the arrays hold what the
+    proxy of the timed steps answers right after them, one response per client connection —
+    each backend's text outside its think block as the tick kernel let it through, and the GPU
+    finalize's joined text — byte for byte what the mock backends stream (qmx_mock
+    --print-expected)."""
+    import importlib.util
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("qmx_bench_dump", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    out = tmp_path / "out"
+    env = dict(os.environ, QMX_BENCH_ENGINE="hip")
+    # the steps span several of the engines' 100 ms counter snapshots, for the breakdown's deltas
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--batch", "65536", "--port", "24100", "--skip-final", "0", "--dump-outputs", str(out)],
+                       cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=180)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert lines, r.stderr[-3000:]
+    res = json.loads(lines[-1])
+    assert r.returncode == 0 and res["valid"] and res["config"]["engine"] == "hip", r.stderr[-2000:]
+    bd = res["breakdown_one_rank"]
+    assert bd["kernel_launches"] > 0 and bd["finalize_items_fused"] > 0 and bd["finalize_host"] == 0, bd
+    assert "harness_ceiling" not in res  # a plain run: --full's checks stay off
+    text = bench.mock_expected(os.path.join(root, "quorum_amd", "bin"))["stream_text"]
+    want = {"content_chatcmpl_parallel_0.npy": text, "content_chatcmpl_parallel_1.npy": text,
+            "content_chatcmpl_parallel_final.npy": ("\n" + "\n-------------\n").join([text, text])}
+    assert sorted(p.name for p in out.iterdir()) == sorted(list(want) + ["status.npy"])
+    status = np.load(out / "status.npy")
+    assert status.shape == (64,) and (status == 200).all(), status
+    for name, t in want.items():
+        a = np.load(out / name)
+        assert a.dtype == np.float32 and a.shape == (64, len(t.encode())), (name, a.shape)
+        assert (a == np.frombuffer(t.encode(), np.uint8)).all(), name
 
 
 def test_gpu_self_spread_rccl_rounds_under_load(tmp_path):

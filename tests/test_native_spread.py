@@ -292,7 +292,12 @@ def test_session_end_during_stalled_round_does_not_block_its_loop():
         env = {"QMX_SPREAD_SELF": "1", "QMX_XCHG_FAULT_STALL_ROUND": "1", "QMX_XCHG_TIMEOUT": "3"}
         with native_cluster(cfg, 1, xchg="tcpbulk", eager=0, run_env=env) as cports:
             base = f"http://127.0.0.1:{cports[0]}"
-            m0 = httpx.get(base + "/metrics").text
+            t0 = time.time()
+            while True:  # a loop publishes its engine's counters with its first sweep, 0.1 s after it starts
+                m0 = httpx.get(base + "/metrics").text
+                if "qmx_engine_free " in m0 or time.time() - t0 > 5:
+                    break
+                time.sleep(0.02)
             body = json.dumps({"messages": MSG, "stream": True}).encode()
             a = socket.create_connection(("127.0.0.1", cports[0]))
             a.sendall(b"POST /chat/completions HTTP/1.1\r\nHost: x\r\nAuthorization: Bearer test-key\r\n"
@@ -500,8 +505,11 @@ def test_spread_remote_deltas_coalesce_client_sends():
         cfg = _cfg(n, block, strategy, [f"http://127.0.0.1:{ports[f'b{i + 1}']}/v1" for i in range(n)])
         req = {"messages": MSG, "stream": True}
         runs = {}
+        # both runs with a 50 ms coalescing deadline: a hold ends at the session's next output, not at
+        # the default 500 us, which these Python upstreams and four ranks sharing a few cores overrun
         for hold in ("1", "0"):
-            with native_cluster(cfg, 4, run_env={"QMX_SESSION_HOLD": hold, "QMX_FINAL_HOLD": hold}) as cports:
+            with native_cluster(cfg, 4, run_env={"QMX_SESSION_HOLD": hold, "QMX_FINAL_HOLD": hold,
+                                                 "QMX_COALESCE_US": "50000"}) as cports:
                 m0 = [httpx.get(f"http://127.0.0.1:{p}/metrics").text for p in cports]
                 bodies = [httpx.post(f"http://127.0.0.1:{cports[0]}/chat/completions", json=req, headers=AUTH,
                                      timeout=30).text for _ in range(24)]

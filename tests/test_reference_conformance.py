@@ -1,9 +1,14 @@
-"""Conformance against the reference ITSELF: the unmodified quorum proxy
-(/root/reference/src/quorum/oai_proxy.py, a scratch copy with only config.yaml written, as
-``bench.py --impl reference`` runs it) and the native C++ server answer the same requests
+"""Conformance against the reference ITSELF: the answers of the unmodified quorum proxy
+(its ``src/quorum/oai_proxy.py``, a scratch copy with only config.yaml written, as
+``bench.py --impl reference`` runs it) and the native C++ server to the same requests
 against the same real-socket fake backends (tests/live_upstream.py), scenario by scenario
 (the table of tests/test_native_server.py: error model, non-stream combine with the usage
 sum, aggregate and its fallback, null abort, malformed events, single-backend passthrough).
+
+The reference's side is a recording, ``tests/golden/reference_conformance.json``: per scenario
+its normalised answer and what its backends received.  With ``QMX_REF_SRC`` naming a reference
+checkout's ``src/quorum`` the reference runs live instead, exactly as it was recorded, and
+``QMX_REF_RECORD=1`` then rewrites the recording.
 
 The native side is otherwise pinned to the builder's FastAPI app (test_native_server.py);
 this file pins it to the reference's own code.  Allowed deviations — each one a SURVEY row —
@@ -41,9 +46,8 @@ import pytest
 import test_native_server as T
 from live_upstream import LiveUpstream
 
-REF_SRC = "/root/reference/src/quorum"
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF_SRC, "oai_proxy.py")),
-                                reason="reference checkout not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_conformance.json")
+REF_SRC = os.environ.get("QMX_REF_SRC", "")  # set: the reference runs live instead of the recording
 
 _n = itertools.count()
 
@@ -92,11 +96,41 @@ def _reference_side(cfg, ups, req, hdrs, tmp_path):
         name, mod = _load_reference(str(root), cfg)
         with TestClient(mod.app) as c:
             r = c.post("/chat/completions", json=req, headers=hdrs)
-        return T._normalize(r.status_code, r.headers.get("content-type"), r.content), live.calls
+        return T._normalize(r.status_code, r.headers.get("content-type"), r.content), _calls(live.calls)
     finally:
         live.close()
         if name:
             _unload(name, root)
+
+
+def _calls(cs):
+    """What the backends received: bodies (model override, suppress flag forwarded) and auth."""
+    return sorted([json.dumps(c["body"], sort_keys=True) if c["body"] else "", c["headers"].get("authorization") or ""]
+                  for c in cs)
+
+
+def _reference(name, cfg, ups, req, hdrs, tmp_path):
+    """The reference's normalised answer to a scenario and what its backends received: from the
+    recording, or live (QMX_REF_SRC; QMX_REF_RECORD=1 also records it)."""
+    if not REF_SRC:
+        with open(GOLDEN) as f:
+            rec = json.load(f)[name]
+        body = bytes.fromhex(rec["body_hex"]) if "body_hex" in rec else rec["body"]
+        return (rec["status"], rec["content_type"], body), rec["calls"]
+    ref, calls = _reference_side(cfg, ups, req, hdrs, tmp_path)
+    if os.environ.get("QMX_REF_RECORD") == "1":
+        try:
+            with open(GOLDEN) as f:
+                golden = json.load(f)
+        except FileNotFoundError:
+            golden = {}
+        rec = {"status": ref[0], "content_type": ref[1], "calls": calls}
+        rec.update({"body_hex": ref[2].hex()} if isinstance(ref[2], bytes) else {"body": ref[2]})
+        golden[name] = rec
+        with open(GOLDEN, "w") as f:
+            json.dump(golden, f, indent=1, sort_keys=True, ensure_ascii=True)
+            f.write("\n")
+    return ref, calls
 
 
 def _whole_body_first_chunk(evs):
@@ -143,7 +177,7 @@ def _per_backend(evs):
 def test_native_matches_reference(name, tmp_path, monkeypatch):
     monkeypatch.delenv("OPENAI_API_KEY", raising=False)  # no_auth: 401 only without the env key
     cfg, ups, req, hdrs = T.SCENARIOS[name]
-    ref, ref_calls = _reference_side(cfg, ups, req, hdrs, tmp_path)
+    ref, ref_calls = _reference(name, cfg, ups, req, hdrs, tmp_path)
     nat, nat_calls = T._native_side(cfg, ups, req, hdrs)
     assert (ref[0], ref[1]) == (nat[0], nat[1]), (name, ref, nat)
     if name in EXCEPTIONS:
@@ -155,8 +189,4 @@ def test_native_matches_reference(name, tmp_path, monkeypatch):
         assert _per_backend(ref[2]) == _per_backend(nat[2]), name
     else:
         assert ref[2] == nat[2], name
-    # what the backends received: bodies (model override, suppress flag forwarded) and auth
-    def calls(cs):
-        return sorted((json.dumps(c["body"], sort_keys=True) if c["body"] else "", c["headers"].get("authorization") or "")
-                      for c in cs)
-    assert calls(ref_calls) == calls(nat_calls), name
+    assert ref_calls == _calls(nat_calls), name

@@ -214,11 +214,11 @@ for l in open('$OUT/kbench.jsonl'):
       cat $OUT/gpuprocs_$n.txt
       [ $rc -eq 0 ] || exit 1 ;;
     multirank=*)
-      n=${step#multirank=}; torchrun_bench multirank_$n $n --steps 5 --warmup 1 --threads 2 --batch 4096 || exit 1 ;;
+      n=${step#multirank=}; torchrun_bench multirank_$n $n --steps 5 --warmup 1 --threads 2 --batch 4096 --full || exit 1 ;;
     selfrank=*)  # bench.py --gpus N launching its own N ranks (no torchrun), sharing GPU 0
       n=${step#selfrank=}
       QMX_BENCH_NDEV=${QMX_BENCH_NDEV:-1} timeout -k 10 400 python bench.py --gpus $n --steps 5 --warmup 1 --threads 2 \
-        --batch 4096 > $OUT/selfrank_$n.json 2> $OUT/selfrank_$n.err
+        --batch 4096 --full > $OUT/selfrank_$n.json 2> $OUT/selfrank_$n.err
       rc=$?; summ selfrank_$n $OUT/selfrank_$n.json
       python3 -c "
 import json
