@@ -497,6 +497,31 @@ PYBIND11_MODULE(_qmx, m) {
       .def("housekeep", &HipGrid::housekeep)
       .def("stop", &HipGrid::stop, py::call_guard<py::gil_scoped_release>())
       .def("stats", &HipGrid::stats);
+  // the thresholds at which the tick kernel and the finalize items switch algorithm, wave
+  // layout or storage width, as compiled (no GPU, no engine): tests/boundary_cases.py places
+  // its inputs on them
+  m.def("kernel_limits", []() {
+    py::dict d;
+    d["BS"] = BS;
+    d["kSpecTile"] = kSpecTile;
+    d["TILE_MAX"] = TILE_MAX;
+    d["MAX_EV"] = MAX_EV;
+    d["MAX_CAND"] = MAX_CAND;
+    d["TOK_CAP"] = TOK_CAP;
+    d["TPL_PRE_MAX"] = TPL_PRE_MAX;
+    d["TPL_SUF_MAX"] = TPL_SUF_MAX;
+    d["kHoleTplBytes"] = kHoleTplBytes;
+    d["kHoleMax"] = kHoleMax;
+    d["kHoleWmaskBytes"] = (int)(sizeof(HoleTpl::wmask) / sizeof(uint32_t)) * 8;
+    d["kBackendTpl"] = kBackendTpl;
+    d["kWindow"] = kWindow;
+    d["kMaxTags"] = kMaxTags;
+    d["kMaxTagLen"] = kMaxTagLen;
+    d["kMaxTail"] = kMaxTail;
+    d["FIN_WIN"] = FIN_WIN;
+    d["FIN_BIG"] = FIN_BIG;
+    return d;
+  });
   m.def("_free_doors", [](HipEngine& e) { return e.free_doors(); });
   m.def("stream_stats", &stream_stats);
   m.def("stream_probe", &stream_probe, py::arg("n"), py::arg("wait_ms") = 200.0,

@@ -33,6 +33,17 @@ struct WorkResult {
   uint32_t pad;
   uint64_t t0, t1;  // s_memrealtime (100 MHz) at workgroup start / end: kernel span per tick
 };
+// Kernel limits: each switches the algorithm, the wave layout or a storage width of the tick
+// kernel / the finalize items (qmx_hip.hip).  The extension reports them (kernel_limits) and
+// the boundary tests take every edge from there, so they move with a retune.
+constexpr int BS = 512;  // 8 waves: S3 spreads events over 8 waves; 2 waves per SIMD hide LDS latency (16 waves measured slower: S3 13.3 -> 15.6 us)
+constexpr int TILE_MAX = 16384;
+constexpr int MAX_EV = 512;  // events per tile (more → WS_MORE requeue); keeps LDS < 80 KiB (two fit a CU's 160 KB: the QMX_GRID_OCC=2 variant)
+constexpr int MAX_CAND = 1024;
+constexpr int kSpecTile = BS * 16;  // tile bytes loaded before the work item is known (16 B per thread: a whole headline stream, ~4.9 KB, in the same PCIe round trip as the item)
+constexpr int TOK_CAP = 512;
+constexpr int FIN_WIN = 8192;   // window bytes: a token is >= 3 bytes, so <= 2731 tokens per window
+constexpr int FIN_BIG = 256;    // kept segments at least this long are copied by the whole workgroup
 constexpr int kTplBytes = 320;  // per-stream event shape template (qmx_lex.h TPL_*)
 struct DevSlot {
   alignas(16) uint8_t tpl[kTplBytes];  // prefix at [0, 256), suffix at [256, 320)
@@ -392,7 +403,8 @@ class HipEngine : public HostEngine {
   std::vector<uint32_t> content_len_;    // device content bytes per slot
   // stats
   std::atomic<uint64_t> escalations_{0}, fin_host_{0}, remote_dev_{0}, remote_staged_{0}, remote_copied_{0},
-      remote_copied_inline_{0}, light_opens_{0};
+      remote_copied_inline_{0}, light_opens_{0},
+      requeues_{0};  // tiles the kernel cut at MAX_EV events (WS_MORE): the rest ran in a later tick
   bool remote_hbm_direct_ = true;
   int spin_us_ = 0;  // QMX_WAIT_SPIN_US: yield-poll before the blocking wait
   bool poll_ = true;  // QMX_WAIT=event: wait on a blocking-sync HIP event instead of polling

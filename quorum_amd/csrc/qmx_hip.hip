@@ -51,13 +51,8 @@ namespace qmx {
                                __FILE__ + ":" + std::to_string(__LINE__));                 \
   } while (0)
 
-constexpr int BS = 512;  // 8 waves: S3 spreads events over 8 waves; 2 waves per SIMD hide LDS latency (16 waves measured slower: S3 13.3 -> 15.6 us)
-constexpr int TILE_MAX = 16384;
-constexpr int MAX_EV = 512;  // events per tile (more → WS_MORE requeue); keeps LDS < 80 KiB (two fit a CU's 160 KB: the QMX_GRID_OCC=2 variant)
-constexpr int MAX_CAND = 1024;
+// BS, TILE_MAX, MAX_EV, MAX_CAND, kSpecTile, TOK_CAP, FIN_WIN, FIN_BIG: qmx_hip.h (kernel limits)
 constexpr int PAD = 16;
-constexpr int kSpecTile = BS * 16;  // tile bytes loaded before the work item is known (16 B per thread: a whole headline stream, ~4.9 KB, in the same PCIe round trip as the item)
-constexpr int TOK_CAP = 512;
 // QMX_STAGE_TIMING record per work item: stamps 0-12, S3 counters 13-20, sub-stage stamps
 // 21 (S3a done), 22 (S3 loop done), 23 (s4_wave: matched), 24 (s4_wave: cuts), 25 (s4_wave:
 // token list + depth scan done), 26 (S6 write: output window filled, host stores next),
@@ -420,6 +415,10 @@ __device__ inline int tok_upper(const Smem& s, int ntok, int x) {
   }
   return lo;
 }
+// A think depth as Smem::tok_dep keeps it: only "== 0" (outside every block) is ever asked of
+// the array, so it saturates instead of wrapping — a stream nested 65536 deep is still
+// inside a block.  The depth a slot carries to its next tick stays a full int (V_NEWDEPTH).
+__device__ __forceinline__ int16_t dep16(int d) { return (int16_t)min(d, 32767); }
 // kept(x) given k = #tokens with pos <= x
 __device__ inline bool kept_at(const Smem& s, int k, int x) {
   if (k > 0 && x < (int)s.tok_pos[k - 1] + (int)s.tok_len[k - 1])
@@ -785,11 +784,11 @@ __device__ bool s4_wave(Smem& s, const uint8_t* Z, int Zn, int ndelta, int depth
       s.tok_pos[k] = (uint16_t)cpos;
       s.tok_id[k] = (int8_t)id;
       s.tok_len[k] = (uint8_t)cplen;
-      s.tok_dep[k] = (int16_t)cdep;
+      s.tok_dep[k] = dep16(cdep);
     }
     if (lane == 63) {
       s.v[V_NTOK] = ntok;
-      s.tok_dep[ntok] = (int16_t)fdep;
+      s.tok_dep[ntok] = dep16(fdep);
     }
   }
   // hold_cut, wave-wide (every lane calls it; `active` lanes get an answer): the last
@@ -2082,12 +2081,13 @@ __device__ __forceinline__ void tick_body(const WorkItem* __restrict__ items, co
           s.tok_pos[k] = s.cand[lane];
           s.tok_id[k] = (int8_t)id;
           s.tok_len[k] = (uint8_t)tok_plen(P, id);
-          s.tok_dep[k] = (int16_t)max(depth0 + ex.x, ex.y);
+          s.tok_dep[k] = dep16(max(depth0 + ex.x, ex.y));
         }
         if (lane == 63) {
-          const int nt = __popcll(m);
+          const int nt = __popcll(m), fdep = max(depth0 + x.x, x.y);
           s.v[V_NTOK] = nt;
-          s.tok_dep[nt] = (int16_t)max(depth0 + x.x, x.y);
+          s.tok_dep[nt] = dep16(fdep);
+          s.v[V_NEWDEPTH] = fdep;  // the slot's depth in full (tok_dep saturates)
         }
       }
       __syncthreads();
@@ -2136,10 +2136,14 @@ __device__ __forceinline__ void tick_body(const WorkItem* __restrict__ items, co
           int k = tid * 4 + i;
           if (k < ntok) {
             int2 f = op(base, pre[i]);
-            s.tok_dep[k] = (int16_t)max(depth0 + f.x, f.y);
+            s.tok_dep[k] = dep16(max(depth0 + f.x, f.y));
           }
         }
-        if (tid == 0) s.tok_dep[ntok] = (int16_t)max(depth0 + tot.x, tot.y);
+        if (tid == 0) {
+          const int fdep = max(depth0 + tot.x, tot.y);
+          s.tok_dep[ntok] = dep16(fdep);
+          s.v[V_NEWDEPTH] = fdep;  // the slot's depth in full (tok_dep saturates)
+        }
       }
       __syncthreads();
     }
@@ -2151,8 +2155,7 @@ __device__ __forceinline__ void tick_body(const WorkItem* __restrict__ items, co
     if (tid == 0) {
       int q;
       hold_cut(s, Z, ncand, ntok, Zn, P, true, &q);
-      s.v[V_NEWTAIL] = q;
-      s.v[V_NEWDEPTH] = s.tok_dep[ntok];
+      s.v[V_NEWTAIL] = q;  // (V_NEWDEPTH: written with the depth scan above)
     }
     __syncthreads();
     // compaction of kept bytes in [0, cutN) into W (= A; input tile no longer needed)
@@ -2477,8 +2480,6 @@ __device__ __forceinline__ void tick_body(const WorkItem* __restrict__ items, co
 // oai_proxy.py:120-139 strip, :834-860 join + final event, :406-423 texts for the aggregator)
 // ------------------------------------------------------------------------------------
 constexpr int FIN_TOK = 4096;   // tag tokens of one tokenisation window staged in LDS
-constexpr int FIN_WIN = 8192;   // window bytes: a token is >= 3 bytes, so <= 2731 tokens per window
-constexpr int FIN_BIG = 256;    // kept segments at least this long are copied by the whole workgroup
 
 struct FinShared {
   int32_t tpos[FIN_TOK];
@@ -4118,6 +4119,7 @@ void HipEngine::complete(HipJob& J, std::vector<SlotResult>& results, std::vecto
         flags |= RF_DONE;
       } else if ((r.status & WS_MORE) || p.submitted < p.carry_len + w.data.size()) {
         J.requeue.push_back(p.slot);  // unprocessed bytes (or a pending EOF) remain
+        if (r.status & WS_MORE) ++requeues_;
       }
     }
     L.d2h_bytes += r.out_len;
@@ -4578,6 +4580,7 @@ std::unordered_map<std::string, double> HipEngine::kernel_stats() {
   m["clk_cycles"] = cyc;  // summable across engines (/metrics sums the io loops' engines)
   m["clk_us"] = cus;
   m["escalations"] = (double)escalations_.load();
+  m["requeues"] = (double)requeues_.load();  // WS_MORE: more events than a tile holds
   m["light_host_opens"] = (double)light_opens_.load();  // streams opened on the host path (latency mode)
   m["fin_host"] = (double)fin_host_.load();
   m["remote_texts_hbm"] = (double)remote_dev_.load();        // spread owner: finals an RCCL round put in HBM

@@ -197,7 +197,7 @@ __device__ inline int wave_lex(const uint8_t* x, int a, int b, uint16_t* tpos, u
 // suffix from its closing quote).  A later event that is byte-identical outside the string
 // and whose middle is a valid JSON string body has the same parse, so its content is the
 // middle -- one 64-lane compare instead of a lex + grammar.  Exact by construction.
-constexpr int TPL_PRE_MAX = 256, TPL_SUF_MAX = 64, TPL_BYTES = TPL_PRE_MAX + TPL_SUF_MAX;
+// TPL_PRE_MAX, TPL_SUF_MAX, TPL_BYTES: qmx_text.h
 
 // x[e0:e0+tp) == tpl[0:tp) and x[e1-ts:e1) == tpl[256:256+ts); tpl 8-byte aligned.
 __device__ inline bool wave_tpl_match(const uint8_t* x, int e0, int e1, const uint8_t* tpl, int tp, int ts) {

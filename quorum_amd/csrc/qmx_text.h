@@ -26,6 +26,9 @@ constexpr int kMaxTags = 16;
 constexpr int kMaxTagLen = 61;   // "</" + 61 + ">" = 64 bytes
 constexpr int kWindow = 16;
 constexpr int kMaxTail = 64;
+// per-stream event shape template (qmx_lex.h): the longest prefix before the content string
+// and suffix after it that are kept
+constexpr int TPL_PRE_MAX = 256, TPL_SUF_MAX = 64, TPL_BYTES = TPL_PRE_MAX + TPL_SUF_MAX;
 constexpr int kJsonMaxDepth = 256;  // deeper == RecursionError (stream abort)
 
 // ---------------------------------------------------------------------------

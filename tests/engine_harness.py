@@ -119,9 +119,14 @@ def split_random(rng: random.Random, data: bytes, max_piece: int = 40) -> List[b
 
 
 def run_engine(engine, streams: Sequence[List[bytes]], filt: Sequence[bool], emit: Sequence[bool],
-               rng: random.Random, strip_final: bool = True, joiner: str = "\n---\n", indices=None):
+               rng: random.Random, strip_final: bool = True, joiner: str = "\n---\n", indices=None,
+               eof_with_last=None, groups=None):
     """Feed chunk lists round-robin with ticks at random points; return per-stream results.
-    ``indices``: each stream's backend index (default i % 7)."""
+    ``indices``: each stream's backend index (default i % 7).  ``eof_with_last``: streams whose
+    end of input arrives with their last chunk, in the same tick (default: one round later).
+    ``groups``: lists of stream numbers, one pair of finalize requests per list — the two
+    finalize results are then lists, one entry per group (default: one request pair over
+    every stream that did not abort)."""
     slots = [engine.open(indices[i] if indices else i % 7, filt[i], emit[i]) for i in range(len(streams))]
     out: Dict[int, List[bytes]] = {s: [] for s in slots}
     flags: Dict[int, int] = {s: 0 for s in slots}
@@ -143,6 +148,9 @@ def run_engine(engine, streams: Sequence[List[bytes]], filt: Sequence[bool], emi
                 engine.feed(slots[i], chunks[cursors[i]])
                 cursors[i] += 1
                 active = True
+                if eof_with_last and eof_with_last[i] and cursors[i] == len(chunks):
+                    engine.finish(slots[i])
+                    cursors[i] += 1
             elif cursors[i] == len(chunks):
                 engine.finish(slots[i])
                 cursors[i] += 1
@@ -152,9 +160,11 @@ def run_engine(engine, streams: Sequence[List[bytes]], filt: Sequence[bool], emi
         if not engine.has_work():
             break
         do_tick()
-    good = [s for s in slots if not (flags[s] & F_ABORTED)]
-    fid = engine.submit_finalize(FinalizeRequest(good, strip_final, "event", joiner, CREATED))
-    fid2 = engine.submit_finalize(FinalizeRequest(good, strip_final, "texts"))
+    fids = []
+    for grp in (groups if groups is not None else [range(len(slots))]):
+        good = [slots[i] for i in grp if not (flags[slots[i]] & F_ABORTED)]
+        fids.append((engine.submit_finalize(FinalizeRequest(good, strip_final, "event", joiner, CREATED)),
+                     engine.submit_finalize(FinalizeRequest(good, strip_final, "texts"))))
     for _ in range(10):
         if not engine.has_work():
             break
@@ -166,7 +176,26 @@ def run_engine(engine, streams: Sequence[List[bytes]], filt: Sequence[bool], emi
                     engine.text(s) if not (flags[s] & F_ABORTED) else ""))
     for s in slots:
         engine.release(s)
-    return res, fin.get(fid), fin.get(fid2)
+    if groups is not None:
+        return res, [fin.get(a) for a, _ in fids], [fin.get(b) for _, b in fids]
+    return res, fin.get(fids[0][0]), fin.get(fids[0][1])
+
+
+class EveryRound:
+    """A tick schedule for run_engine's ``rng``: a tick after every round of feeds, so chunk k
+    of every stream is processed by tick k (cases that need a fixed schedule)."""
+
+    @staticmethod
+    def random() -> float:
+        return 0.0
+
+
+def run_case(engine, case, strip_final: bool = True, tick_seed: int = 1):
+    """One boundary case (tests/boundary_cases.py Case) through any engine."""
+    rng = EveryRound() if case.every_round else random.Random(tick_seed)
+    return run_engine(engine, case.streams, case.filt, case.emit, rng, strip_final=strip_final,
+                      joiner=case.joiner, indices=case.indices, eof_with_last=case.eof_with_last,
+                      groups=case.groups)
 
 
 def python_engine(tags):
@@ -193,3 +222,27 @@ def rand_json(rng, depth=0):
                           rng.randint(0, 3))
         return "{" + ", ".join(f"{k}: {rand_json(rng, depth + 1)}" for k in keys) + "}"
     return "[" + ", ".join(rand_json(rng, depth + 1) for _ in range(rng.randint(0, 3))) + "]"
+
+
+_oracle = {}
+
+
+def oracle_result(case, strip_final: bool = True):
+    """The python oracle's result of a boundary case: computed once, shared by every test
+    that compares with it, never changed."""
+    key = (case.name, strip_final)
+    if key not in _oracle:
+        _oracle[key] = run_case(PyEngine(case.tags), case, strip_final)
+    return _oracle[key]
+
+
+def assert_same(got, want, case, what):
+    """Byte-exact equality of two run_case results, stream by stream."""
+    (g, gf, gt), (w, wf, wt) = got, want
+    assert len(g) == len(w) == len(case.streams)
+    for i, (a, b) in enumerate(zip(g, w)):
+        assert a[1] == b[1], (what, case.name, "flags", i)
+        assert a[0] == b[0], (what, case.name, "sse", i)
+        assert a[2] == b[2], (what, case.name, "text", i)
+    assert gf == wf, (what, case.name, "final event")
+    assert gt == wt, (what, case.name, "final texts")

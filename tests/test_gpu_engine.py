@@ -12,6 +12,7 @@ from quorum_amd.ops.engine import F_ABORTED, F_DONE, FinalizeRequest
 from quorum_amd.ops.native import NativeEngine
 
 import engine_harness as H
+from boundary_cases import HOLE_NUM, HOLE_STR, _oai_event
 
 pytestmark = pytest.mark.gpu
 
@@ -448,23 +449,6 @@ def test_hip_completion_modes(ext, monkeypatch):
     eng.release(slot)
     monkeypatch.setenv("QMX_WAIT", "event")
     _check(7002, 40)
-
-
-def _oai_event(id_, created, model, delta, finish=b"null", compact=False):
-    sep = b"," if compact else b", "
-    col = b":" if compact else b": "
-    obj = (b"{" + b'"id"' + col + b'"' + id_ + b'"' + sep + b'"object"' + col + b'"chat.completion.chunk"' + sep +
-           b'"created"' + col + created + sep + b'"model"' + col + b'"' + model + b'"' + sep + b'"choices"' + col +
-           b'[{"index"' + col + b"0" + sep + b'"delta"' + col + delta + sep + b'"logprobs"' + col + b"null" + sep +
-           b'"finish_reason"' + col + finish + b"}]}")
-    return b"data: " + obj + b"\n\n"
-
-
-# hole contents: valid and invalid string bodies / numbers, type changes
-HOLE_STR = [b"abc", b"", b'q\\"x', b"\\u00e9\\ud83d\\ude00", b"\xc3\xa9 ok", b"bad\xff", b"tail\\\\", b"a\\", b"x\x01y",
-            b"\\uZZZZ", b"<think>", b"</think>", b"e\\nf", b"\\/", b"\xe4\xb8\xad" * 20, b"q" * 120]
-HOLE_NUM = [b"1700000000", b"0", b"-1", b"01", b"1.5e3", b"-", b"1e400", b"123456789012345678901234567890123456",
-            b"2.", b"-0", b"1E+2", b"true", b"null", b'"1700000000"']
 
 
 def test_hip_hole_templates(ext, monkeypatch):
