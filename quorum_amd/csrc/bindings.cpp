@@ -25,7 +25,7 @@ namespace {
 struct PyStreamFilter {
   TagSet ts;
   FilterState fs;
-  explicit PyStreamFilter(const std::vector<std::string>& tags) : ts(make_tagset(tags)) {}
+  PyStreamFilter(const std::vector<std::string>& tags, bool classes) : ts(make_tagset(tags, classes)) {}
   py::bytes feed(const std::string& s) {
     std::string out;
     filter_feed(ts, fs, (const uint8_t*)s.data(), s.size(), out);
@@ -39,7 +39,7 @@ struct PyStreamFilter {
 
 struct PyStripper {
   TagSet ts;
-  explicit PyStripper(const std::vector<std::string>& tags) : ts(make_tagset(tags)) {}
+  PyStripper(const std::vector<std::string>& tags, bool classes) : ts(make_tagset(tags, classes)) {}
   py::bytes strip(const std::string& s) { return py::bytes(strip_final(ts, (const uint8_t*)s.data(), s.size())); }
 };
 
@@ -137,6 +137,7 @@ ServerCfg server_cfg_from(const py::dict& d) {
   gs("separator", c.separator); gb("hide_intermediate", c.hide_intermediate); gb("hide_final", c.hide_final);
   gb("skip_final", c.skip_final); gb("suppress", c.suppress);
   if (d.contains("tags")) c.tags = py::cast<std::vector<std::string>>(d["tags"]);
+  gb("tag_classes", c.tag_classes);
   gs("aggregator_name", c.aggregator_name); gs("prompt_template", c.prompt_template);
   gs("intermediate_separator", c.intermediate_separator); gs("query_format", c.query_format);
   gs("source_label_format", c.source_label_format); gb("include_original_query", c.include_original_query);
@@ -474,18 +475,42 @@ PYBIND11_MODULE(_qmx, m) {
     return py::bytes(out);
   });
   py::class_<PyStreamFilter>(m, "StreamFilter")
-      .def(py::init<const std::vector<std::string>&>())
+      .def(py::init<const std::vector<std::string>&, bool>(), py::arg("tags"), py::arg("classes") = false)
       .def("feed", &PyStreamFilter::feed)
       .def("flush", &PyStreamFilter::flush);
   py::class_<PyStripper>(m, "Stripper")
-      .def(py::init<const std::vector<std::string>&>())
+      .def(py::init<const std::vector<std::string>&, bool>(), py::arg("tags"), py::arg("classes") = false)
       .def("strip", &PyStripper::strip);
+  // is this tag list inside what make_tagset runs natively (the one definition of the subset)?
+  m.def("tagset_ok", [](const std::vector<std::string>& tags, bool classes) {
+    try {
+      make_tagset(tags, classes);
+      return true;
+    } catch (const std::invalid_argument&) {
+      return false;
+    }
+  }, py::arg("tags"), py::arg("classes") = false);
+  // candidates '<' of `text` the GPU kernels would hand to the host path (qmx_text.h
+  // class_candidate, the shared suspect rule), with the streaming or the strip tables
+  m.def("class_suspects", [](const std::vector<std::string>& tags, const std::string& text, bool strip) {
+    const TagSet ts = make_tagset(tags, true);
+    int k = 0;
+    const TagClasses* tc = tag_classes(ts);
+    if (tc == nullptr) return k;
+    const uint8_t* x = (const uint8_t*)text.data();
+    for (int p = 0; p < (int)text.size(); ++p) {
+      int tok = 0, len = 0;
+      if (x[p] == '<' && class_candidate(x, (int)text.size(), p, ts, *tc, strip, &tok, &len) == CC_SUSPECT) ++k;
+    }
+    return k;
+  }, py::arg("tags"), py::arg("text"), py::arg("strip") = false);
   env_refresh();
   py::class_<CpuEngine> ce(m, "CpuEngine");
-  ce.def(py::init([](const std::vector<std::string>& tags) {
-    env_refresh();
-    return new CpuEngine(tags);
-  }));
+  ce.def(py::init([](const std::vector<std::string>& tags, bool classes) {
+           env_refresh();
+           return new CpuEngine(tags, classes);
+         }),
+         py::arg("tags"), py::arg("classes") = false);
   bind_engine(ce);
   // the multi-door grid of loop ticks (tests drive several door engines from Python threads)
   py::class_<HipGrid>(m, "HipGrid")
@@ -528,13 +553,13 @@ PYBIND11_MODULE(_qmx, m) {
         py::call_guard<py::gil_scoped_release>());
   py::class_<HipEngine> he(m, "HipEngine");
   he.def(py::init([](const std::vector<std::string>& tags, int device, int tile, int max_slots, int content_cap,
-                      int lanes, HipGrid* grid, int door, int ndoors) {
+                      int lanes, HipGrid* grid, int door, int ndoors, bool classes) {
            env_refresh();
-           return new HipEngine(tags, device, tile, max_slots, content_cap, lanes, grid, door, ndoors);
+           return new HipEngine(tags, device, tile, max_slots, content_cap, lanes, grid, door, ndoors, classes);
          }),
          py::arg("tags"), py::arg("device"), py::arg("tile_bytes") = 16384, py::arg("max_slots") = 8192,
          py::arg("content_cap") = 1 << 20, py::arg("lanes") = 1, py::arg("grid") = nullptr, py::arg("door") = -1,
-         py::arg("ndoors") = 1, py::keep_alive<1, 8>());
+         py::arg("ndoors") = 1, py::arg("classes") = false, py::keep_alive<1, 8>());
   bind_engine(he);
   he.def("kernel_stats", &HipEngine::kernel_stats);
   he.def("debug_poison_results", &HipEngine::debug_poison_results, py::arg("ahead") = 1);

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <stdexcept>
 
 namespace qmx {
@@ -15,9 +16,116 @@ namespace qmx {
 const char* kDeltaSuffix = "\"}, \"finish_reason\": null}]}\n\n";
 const char* kFinalSuffix = "\"}, \"finish_reason\": \"stop\"}]}\n\n";
 
-TagSet make_tagset(const std::vector<std::string>& tags) {
+namespace {
+
+// One parsed element of a class tag: a literal byte, or an ASCII acceptance table.
+struct Elem {
+  bool cls = false;
+  uint8_t lit = 0;
+  uint32_t tab[4] = {0, 0, 0, 0};
+  uint8_t flags = 0;
+};
+
+bool printable(uint8_t c) { return c >= 0x20 && c < 0x7f; }
+
+void tab_set(uint32_t* tab, uint8_t c) {  // under IGNORECASE: both cases of a letter
+  for (uint8_t v : {c, lower_ascii(c), (uint8_t)((c >= 'a' && c <= 'z') ? c - 32 : c)}) tab[v >> 5] |= 1u << (v & 31);
+}
+
+// "[...]" at t[i] == '[': members are printable ASCII literals other than "<>/[", ranges and
+// the escapes \\ \] \^ \- \[.  False for everything Python's parser reads differently or
+// warns about (a leading ']', "--", "&&", "~~", "||", shorthands, POSIX classes).
+bool parse_bracket(const std::string& t, size_t& i, Elem& e) {
+  size_t j = i + 1;
+  bool neg = false;
+  if (j < t.size() && t[j] == '^') { neg = true; ++j; }
+  if (j < t.size() && t[j] == ']') return false;
+  uint32_t tab[4] = {0, 0, 0, 0};
+  // one member byte at t[j] (escapes resolved); '-' is handled by the caller
+  auto member = [&](uint8_t* out) {
+    if (j >= t.size()) return false;
+    uint8_t c = (uint8_t)t[j];
+    if (c == '\\') {
+      if (j + 1 >= t.size() || !std::strchr("\\]^-[", t[j + 1])) return false;
+      *out = (uint8_t)t[j + 1];
+      j += 2;
+      return true;
+    }
+    if (!printable(c) || std::strchr("<>/[]", (int)c)) return false;
+    *out = c;
+    ++j;
+    return true;
+  };
+  const size_t first = j;
+  while (true) {
+    if (j >= t.size()) return false;  // no closing ']'
+    if (t[j] == ']') break;
+    if (j + 1 < t.size() && t[j] == t[j + 1] && std::strchr("-&~|", t[j])) return false;
+    if (t[j] == '-') {  // a literal only as the first or the last member
+      if (j != first && !(j + 1 < t.size() && t[j + 1] == ']')) return false;
+      tab_set(tab, '-');
+      ++j;
+      continue;
+    }
+    uint8_t lo;
+    if (!member(&lo)) return false;
+    if (j + 1 < t.size() && t[j] == '-' && t[j + 1] != ']') {  // range lo-hi
+      ++j;
+      if (t[j] == '-') return false;
+      uint8_t hi;
+      if (!member(&hi) || hi < lo) return false;
+      for (int c = lo; c <= hi; ++c) tab_set(tab, (uint8_t)c);
+    } else {
+      tab_set(tab, lo);
+    }
+  }
+  i = j + 1;
+  e.cls = true;
+  e.flags = neg ? CLS_WIDE : 0;
+  for (int k = 0; k < 4; ++k) e.tab[k] = neg ? ~tab[k] : tab[k];
+  return true;
+}
+
+// The elements of one tag, or false when it lies outside the class subset.
+bool parse_class_tag(const std::string& t, std::vector<Elem>& out) {
+  for (size_t i = 0; i < t.size();) {
+    const uint8_t c = (uint8_t)t[i];
+    Elem e;
+    if (c == '\\') {
+      if (i + 1 >= t.size() || !std::strchr(".^$*+?{}[]\\|()-", t[i + 1])) return false;
+      e.lit = (uint8_t)t[i + 1];
+      i += 2;
+    } else if (c == '.') {
+      e.cls = true;
+      e.flags = CLS_WIDE | CLS_DOT;
+      for (int k = 0; k < 4; ++k) e.tab[k] = ~0u;
+      ++i;
+    } else if (c == '[') {
+      if (!parse_bracket(t, i, e)) return false;
+    } else {
+      if (!printable(c) || std::strchr("^$*+?{}]|()<>/", (int)c)) return false;
+      e.lit = lower_ascii(c);
+      ++i;
+    }
+    out.push_back(e);
+  }
+  return !out.empty() && !out[0].cls;
+}
+
+// the TagClasses of every class tag set this process has made (TagSet keeps the id + 1)
+constexpr int kClsPool = 255;
+std::mutex cls_mu;
+TagClasses* cls_pool[kClsPool];
+int cls_n = 0;
+
+}  // namespace
+
+TagSet make_tagset(const std::vector<std::string>& tags, bool classes) {
   TagSet ts;
   std::memset(&ts, 0, sizeof(ts));
+  TagClasses tc;
+  std::memset(&tc, 0, sizeof(tc));
+  bool any_cls = false;
   std::vector<std::string> seen;
   for (const auto& t0 : tags) {
     std::string t;
@@ -27,20 +135,77 @@ TagSet make_tagset(const std::vector<std::string>& tags) {
     // 271-274); '<', '>' and '/' in a tag let one tag's pattern start inside another's, so
     // the token model (at most one pattern per '<') would not hold; non-ASCII would need
     // Unicode case folding.  Everything else is literal, exactly as in the regex.
+    bool literal = true;
     for (char ch : t) {
       const uint8_t c = (uint8_t)ch;
       const bool ok = c >= 0x20 && c < 0x7f && !std::strchr(".^$*+?{}[]\\|()<>/", (int)c);
-      if (!ok) throw std::invalid_argument("tag needs regex semantics: " + t0);
+      if (!ok) literal = false;
     }
-    if (t.empty() || (int)t.size() > kMaxTagLen) throw std::invalid_argument("unsupported tag length: " + t0);
+    if (t.empty() || (int)t.size() > kMaxTagLen) {
+      if (!literal) throw std::invalid_argument("tag needs regex semantics: " + t0);
+      throw std::invalid_argument("unsupported tag length: " + t0);
+    }
+    std::vector<Elem> elems;
+    if (!literal) {
+      // class tags: '.', [...] and escaped punctuation, one code point per element; the
+      // tables come from the tag as written (IGNORECASE makes its case immaterial)
+      if (!classes || !parse_class_tag(t0, elems)) throw std::invalid_argument("tag needs regex semantics: " + t0);
+      int bound = 3;  // bytes of the longest "</" + match + ">"
+      for (const Elem& e : elems) bound += (e.flags & CLS_WIDE) ? 4 : 1;
+      if (bound > kMaxTail) throw std::invalid_argument("unsupported tag length: " + t0);
+    }
     if (ts.n >= kMaxTags) throw std::invalid_argument("too many thinking tags");
     seen.push_back(t);
-    ts.len[ts.n] = (int)t.size();
-    std::memcpy(ts.name[ts.n], t.data(), t.size());
+    tc.srclen[ts.n] = (int)t.size();
+    std::memcpy(tc.src[ts.n], t.data(), t.size());
+    if (literal) {
+      ts.len[ts.n] = (int)t.size();
+      std::memcpy(ts.name[ts.n], t.data(), t.size());
+    } else {
+      any_cls = true;
+      ts.len[ts.n] = (int)elems.size();
+      for (size_t i = 0; i < elems.size(); ++i) {
+        const Elem& e = elems[i];
+        if (!e.cls) {
+          ts.name[ts.n][i] = e.lit;
+          continue;
+        }
+        int k = 0;
+        while (k < tc.n && !(tc.flags[k] == e.flags && std::memcmp(tc.tab[k], e.tab, sizeof(e.tab)) == 0)) ++k;
+        if (k == tc.n) {
+          if (tc.n >= kMaxClasses) throw std::invalid_argument("too many tag classes");
+          std::memcpy(tc.tab[k], e.tab, sizeof(e.tab));
+          tc.flags[k] = e.flags;
+          ++tc.n;
+        }
+        ts.name[ts.n][i] = (uint8_t)(0x80 + k);
+      }
+    }
     ++ts.n;
   }
   if (ts.n == 0) throw std::invalid_argument("empty tag set");
+  if (any_cls) {
+    // interned: TagSet is copied by value everywhere (kernel parameters included) and keeps
+    // only the id; the tables live for the process, one entry per distinct class tag set
+    std::lock_guard<std::mutex> g(cls_mu);
+    int id = 0;
+    for (int k = 0; k < cls_n && id == 0; ++k)
+      if (std::memcmp(cls_pool[k], &tc, sizeof(tc)) == 0) id = k + 1;
+    if (id == 0) {
+      if (cls_n >= kClsPool) throw std::invalid_argument("too many distinct class tag sets in one process");
+      cls_pool[cls_n] = new TagClasses(tc);
+      id = ++cls_n;
+    }
+    ts.name[0][kMaxTagLen] = (uint8_t)id;
+  }
   return ts;
+}
+
+const TagClasses* tag_classes(const TagSet& ts) {
+  const int id = tagset_cls_id(ts);
+  if (id == 0) return nullptr;
+  std::lock_guard<std::mutex> g(cls_mu);
+  return cls_pool[id - 1];
 }
 
 // --------------------------------------------------------------------------------
@@ -55,12 +220,14 @@ void filter_feed(const TagSet& ts, FilterState& fs, const uint8_t* text, size_t 
   int N = (int)xs.size();
   int i = 0;
   fs.tail_len = 0;
+  const TagClasses* tc = tag_classes(ts);
+  const bool cls = tc != nullptr;
   while (true) {
     // next token at or after i (depth 0: opens only are tokens)
     int p = i, tok = 0, L = 0;
     for (; p < N; ++p) {
       if (x[p] != '<') continue;
-      tok = match_at(x, N, p, ts, &L);
+      tok = cls ? class_match_at(x, N, p, ts, *tc, false, &L) : match_at(x, N, p, ts, &L);
       if (tok > 0 || (tok < 0 && fs.depth > 0)) break;
       tok = 0;
     }
@@ -76,8 +243,18 @@ void filter_feed(const TagSet& ts, FilterState& fs, const uint8_t* text, size_t 
     }
     // no more tokens: hold back a trailing partial tag from the LAST '<'
     int q = N - 1;
-    while (q >= i && x[q] != '<') --q;
-    bool hold = q >= i && pattern_prefix(x, q, N, ts, fs.depth == 0);
+    bool hold;
+    if (cls && fs.depth > 0) {
+      // class tags inside a block: a class element may swallow a later '<', so keep from the
+      // EARLIEST '<' whose rest is still a proper prefix of some pattern (the reference keeps
+      // its whole buffer here; the byte bound of make_tagset keeps this within kMaxTail)
+      for (q = i; q < N; ++q)
+        if (x[q] == '<' && class_prefix(x, q, N, ts, *tc)) break;
+      hold = q < N;
+    } else {
+      while (q >= i && x[q] != '<') --q;
+      hold = q >= i && (cls ? source_prefix(x, q, N, ts, *tc) : pattern_prefix(x, q, N, ts, fs.depth == 0));
+    }
     int cut = hold ? q : N;
     if (fs.depth == 0) out.append((const char*)x + i, cut - i);
     if (hold) {
@@ -91,7 +268,52 @@ void filter_feed(const TagSet& ts, FilterState& fs, const uint8_t* text, size_t 
 // --------------------------------------------------------------------------------
 // final strip: tokens, per-tag next-close links, leftmost-first walk, Unicode strip
 // --------------------------------------------------------------------------------
+// Class tags: re.sub("<(alt)>.*?</\1>", "", I|S) as the backtracking matcher runs it.  At each
+// start every alternative is tried in order; its close is the first later "</" + the text the
+// open captured + ">" (ASCII case folded, compared with the captured bytes, not the pattern);
+// an alternative without a close gives way to the next one.  The closes are indexed once by
+// (tag, folded capture) — a text equal to a capture of tag t matches t's elements too — so the
+// walk stays near linear where the regex is quadratic.
+static std::string strip_final_classes(const TagSet& ts, const TagClasses& tc, const uint8_t* x, int n) {
+  auto key_of = [&](int t, int a, int b) {
+    std::string k(1, (char)t);
+    for (int i = a; i < b; ++i) k.push_back((char)lower_ascii(x[i]));
+    return k;
+  };
+  std::unordered_map<std::string, std::vector<int>> closes;  // -> positions of the "</", ascending
+  for (int p = 0; p + 1 < n; ++p) {
+    if (x[p] != '<' || x[p + 1] != '/') continue;
+    for (int t = 0; t < ts.n; ++t) {
+      int end = 0;
+      if (class_walk(x, n, p, ts, tc, ts.n + t, true, &end) == 1) closes[key_of(t, p + 2, end - 1)].push_back(p);
+    }
+  }
+  std::string out;
+  out.reserve(n);
+  int i = 0;
+  for (int p = 0; p < n; ++p) {
+    if (x[p] != '<') continue;
+    for (int t = 0; t < ts.n; ++t) {
+      int end = 0;
+      if (class_walk(x, n, p, ts, tc, t, true, &end) != 1) continue;
+      auto it = closes.find(key_of(t, p + 1, end - 1));
+      if (it == closes.end()) continue;
+      auto c = std::lower_bound(it->second.begin(), it->second.end(), end);
+      if (c == it->second.end()) continue;
+      out.append((const char*)x + i, p - i);
+      i = *c + 2 + (end - 1 - (p + 1)) + 1;
+      p = i - 1;
+      break;
+    }
+  }
+  out.append((const char*)x + i, n - i);
+  int a = 0, b = (int)out.size();
+  ustrip((const uint8_t*)out.data(), &a, &b);
+  return out.substr(a, b - a);
+}
+
 std::string strip_final(const TagSet& ts, const uint8_t* x, size_t n) {
+  if (const TagClasses* tc = tag_classes(ts)) return strip_final_classes(ts, *tc, x, (int)n);
   struct Tok { int pos, len, id; };
   std::vector<Tok> toks;
   for (int p = 0; p < (int)n; ++p) {
@@ -313,7 +535,7 @@ static double mono_s() {
   return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
-HostEngine::HostEngine(const std::vector<std::string>& tags) : ts_(make_tagset(tags)) {
+HostEngine::HostEngine(const std::vector<std::string>& tags, bool classes) : ts_(make_tagset(tags, classes)) {
   if (const char* pe = env_get("QMX_PIPELINE")) pipeline_ = atoi(pe) != 0;
 }
 
@@ -595,7 +817,7 @@ struct AsyncCpuEngine::Done {
   std::atomic<bool> ready{false};
 };
 
-AsyncCpuEngine::AsyncCpuEngine(const std::vector<std::string>& tags) : CpuEngine(tags) {
+AsyncCpuEngine::AsyncCpuEngine(const std::vector<std::string>& tags, bool classes) : CpuEngine(tags, classes) {
   th_ = std::thread([this] { run(); });
 }
 

@@ -28,7 +28,10 @@ namespace qmx {
 
 enum ResultFlags : int { RF_DONE = 1, RF_ABORTED = 2, RF_ESCALATED = 4 };
 
-TagSet make_tagset(const std::vector<std::string>& tags);
+// classes: also accept class tags ("." / "[...]" / escaped punctuation; qmx_text.h TagClasses)
+TagSet make_tagset(const std::vector<std::string>& tags, bool classes = false);
+// the class tables and source text of a class tag set (null for a literal one)
+const TagClasses* tag_classes(const TagSet& ts);
 
 struct FilterState {
   int depth = 0;
@@ -158,7 +161,7 @@ class SlotTable {
 
 class HostEngine {
  public:
-  explicit HostEngine(const std::vector<std::string>& tags);
+  explicit HostEngine(const std::vector<std::string>& tags, bool classes = false);
   virtual ~HostEngine() = default;
 
   // returns the slot; *gen (optional) receives the slot's open generation (SlotResult::gen)
@@ -283,7 +286,7 @@ class HostEngine {
 
 class CpuEngine : public HostEngine {
  public:
-  explicit CpuEngine(const std::vector<std::string>& tags) : HostEngine(tags) {}
+  explicit CpuEngine(const std::vector<std::string>& tags, bool classes = false) : HostEngine(tags, classes) {}
   // pipelined lanes on the CPU: the whole tick runs in job_complete (exercises GpuHub's
   // pipelined loop without a GPU)
   bool pipelined() const override { return pipeline_; }
@@ -303,7 +306,7 @@ class CpuEngine : public HostEngine {
 // CPU and TSan suites, where no GPU is.
 class AsyncCpuEngine : public CpuEngine {
  public:
-  explicit AsyncCpuEngine(const std::vector<std::string>& tags);
+  explicit AsyncCpuEngine(const std::vector<std::string>& tags, bool classes = false);
   ~AsyncCpuEngine() override;
   bool async_jobs() const override { return true; }
   void job_post(Job& j) override;

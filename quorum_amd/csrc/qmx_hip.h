@@ -92,13 +92,18 @@ struct BackendTpl {
 // WF_PUBLISH: the tick's first item of its backend index — the one workgroup that writes that
 // backend's event-shape / hole templates for the lane's next launch
 enum WorkFlags : uint32_t { WF_EOF = 1, WF_FILTER = 2, WF_EMIT = 4, WF_STARTED = 8, WF_FRESH = 16, WF_PUBLISH = 32 };
-enum WorkStatus : uint32_t { WS_DONE = 1, WS_ABORTED = 2, WS_STARTED = 4, WS_ESCALATE = 8, WS_MORE = 16 };
+// WS_CLASS (with WS_ESCALATE): class tags, an ambiguous window — the exact host path decides
+enum WorkStatus : uint32_t { WS_DONE = 1, WS_ABORTED = 2, WS_STARTED = 4, WS_ESCALATE = 8, WS_MORE = 16, WS_CLASS = 32 };
 
 struct KParams {
   TagSet ts;
   int npat;
   int32_t pat_E[2 * kMaxTags];  // Σ_j m(q0²+q1²) over the window part of each pattern (match iff dot == -E)
   int32_t plen[2 * kMaxTags];   // pattern_len(ts, t), 0 past npat (a load with no dependence on ts.n)
+  // class tags (qmx_text.h TagClasses, in device memory; null for a literal tag set): the
+  // tables and source text, read only where a class tag set needs them.  (In what was padding
+  // before `code`: the parameters' layout is the literal tag sets'.)
+  const TagClasses* cls;
   // byte → matcher code: 1..94 for the bytes that occur in patterns (letters folded), 95 for
   // every other byte (never equal to a pattern byte), 0 past the end of the text
   alignas(16) uint8_t code[256];
@@ -303,7 +308,7 @@ class HipEngine : public HostEngine {
  public:
   // grid: loop-tick mode — one lane whose ticks go to door `door` of a shared multi-door grid
   HipEngine(const std::vector<std::string>& tags, int device, int tile_bytes, int max_slots, int content_cap,
-            int lanes = 1, HipGrid* grid = nullptr, int door = -1, int ndoors = 1);
+            int lanes = 1, HipGrid* grid = nullptr, int door = -1, int ndoors = 1, bool classes = false);
   ~HipEngine() override;
   // loop-tick mode (the io loop drives its own ticks): has the posted job's every result been
   // published?  Never blocks.  expect_us: the job's expected remaining time (poll timing).
@@ -394,6 +399,7 @@ class HipEngine : public HostEngine {
   // device-resident
   DevSlot* d_state_ = nullptr;
   uint8_t* d_content_ = nullptr;
+  TagClasses* d_cls_ = nullptr;  // class tags: tables + source text (KParams::cls)
   // host mirrors (per slot; a slot is only touched by the lane it is busy on)
   std::vector<uint8_t> host_mode_;       // slot escalated to the host path
   // spread owner: a remote stream's final text that came over the mesh, held in the slot's
@@ -404,7 +410,8 @@ class HipEngine : public HostEngine {
   // stats
   std::atomic<uint64_t> escalations_{0}, fin_host_{0}, remote_dev_{0}, remote_staged_{0}, remote_copied_{0},
       remote_copied_inline_{0}, light_opens_{0},
-      requeues_{0};  // tiles the kernel cut at MAX_EV events (WS_MORE): the rest ran in a later tick
+      requeues_{0},  // tiles the kernel cut at MAX_EV events (WS_MORE): the rest ran in a later tick
+      class_escalations_{0}, class_fin_host_{0};  // class tags: ambiguous windows handed to the host path
   bool remote_hbm_direct_ = true;
   int spin_us_ = 0;  // QMX_WAIT_SPIN_US: yield-poll before the blocking wait
   bool poll_ = true;  // QMX_WAIT=event: wait on a blocking-sync HIP event instead of polling

@@ -140,7 +140,8 @@ enum : int {
   V_NTOK, V_BAIL, V_DEPTH0, V_TAILLEN, V_NEWTAIL, V_NEWDEPTH, V_WLEN, V_NEMIT, V_ETOT, V_OUTLEN,
   V_TPLPRE, V_TPLSUF, V_TPLK, V_NEXTEV, V_NFULL, V_NTPL, V_CFULL, V_CTPL, V_CLEX, V_NHOLE, V_CHOLE, V_S4W,
   V_HCLAIM,  // hole-template slots this workgroup wrote (bit per slot): one writer per slot
-  V_S6W      // the sizing ran on wave 0 right after s4_wave
+  V_S6W,     // the sizing ran on wave 0 right after s4_wave
+  V_CLS      // class tags: a candidate or a holdback of this tile is ambiguous (host path)
 };
 
 // LDS byte reader that fetches one aligned 64-bit word per 8 sequential bytes: a byte-serial
@@ -448,8 +449,43 @@ __device__ inline bool pattern_prefix_w(const uint8_t* Z, int q, int e, const KP
   return false;
 }
 
+// ------------------------------------------------------------------------------------
+// class tags (KParams::cls != null)
+// ------------------------------------------------------------------------------------
+// Everything a class tag set adds is compiled under `CLS`, into a kernel of its own
+// (qmx_ctick_kernel): the literal tag sets' kernels are the code they were, registers and
+// all (tests/test_isa.py), and an engine with a class tag set launches the other one.
+// The fast matchers compare bytes for equality, and a class position of a pattern holds
+// 0x80 + class index — no byte of a window that is not suspect — so they keep matching the
+// literal tags and the class tags come from the shared walk (qmx_text.h class_candidate), one
+// candidate per thread, its tables read from the tag classes in global memory.  Returns the
+// candidate's token — `lit` (the fast matcher's), or the class tag's when it comes first in the
+// tag list — or kClsSuspect.
+constexpr int kClsSuspect = 0x100;
+__device__ __forceinline__ int class_token(const uint8_t* Z, int Zn, int p, const KParams& P, int lit) {
+  int tok = 0, len = 0;
+  const int r = class_candidate(Z, Zn, p, P.ts, *P.cls, false, &tok, &len);
+  if (r == CC_SUSPECT) return kClsSuspect;
+  if (r == CC_MATCH && (lit == 0 || abs(tok) < abs(lit))) return tok;
+  return lit;
+}
+// The holdback's prefix test for Z[q, e), the last '<' before e that is no completed token
+// (tk: the token that completes later in Z, 0: none; dq: the depth before it).  Outside a
+// block the reference holds what is a prefix of a tag's SOURCE text, so an open tag whose
+// first part was released at this cut is no token at all: bit 1, the tile goes to the host.
+// Inside a block: a proper class-aware prefix of any pattern.  Bit 0: hold.
+__device__ __forceinline__ int class_hold(const uint8_t* Z, int q, int e, const KParams& P, int dq, int tk) {
+  if (e - q > kMaxTail) return 0;
+  if (dq == 0) {
+    const bool pre = source_prefix(Z, q, e, P.ts, *P.cls);
+    return (pre ? 1 : 0) | (tk > 0 && !pre ? 2 : 0);
+  }
+  return class_prefix(Z, q, e, P.ts, *P.cls) ? 1 : 0;
+}
+
 // holdback test at stream position e (Z coords): returns cut (q when held, else e).
 // opens_only=false also reports any-pattern prefixes at depth > 0 (tail carry).
+template <bool CLS>
 __device__ inline int hold_cut(const Smem& s, const uint8_t* Z, int ncand, int ntok, int e, const KParams& P,
                                bool for_tail, int* q_out) {
   int lo = 0, hi = ncand;  // last candidate index with cand < e
@@ -465,7 +501,14 @@ __device__ inline int hold_cut(const Smem& s, const uint8_t* Z, int ncand, int n
   int tk = s.cand_tok[idx];
   if (tk != 0 && q + tok_plen(P, tk) <= e) return e;  // completed token
   int dq = s.tok_dep[tok_lower(s, ntok, q)];
-  bool pre = pattern_prefix_w(Z, q, e, P, dq == 0);
+  bool pre;
+  if constexpr (CLS) {
+    const int r = class_hold(Z, q, e, P, dq, tk);
+    if (r & 2) const_cast<Smem&>(s).v[V_CLS] = 1;  // (the one write: the literal kernels' hold_cut reads only)
+    pre = r & 1;
+  } else {
+    pre = pattern_prefix_w(Z, q, e, P, dq == 0);
+  }
   if (!pre) return e;
   if (dq == 0 || for_tail) {
     *q_out = q;
@@ -1149,6 +1192,7 @@ __device__ inline void s6_size_wave(Smem& s, const uint8_t* W, int Wlen, int nde
   }
 }
 
+template <bool CLS>
 __device__ __forceinline__ void tick_body(const WorkItem* __restrict__ items, const uint8_t* __restrict__ in,
                                           uint8_t* __restrict__ out, WorkResult* __restrict__ res,
                                           DevSlot* __restrict__ state, uint8_t* __restrict__ content,
@@ -1204,6 +1248,7 @@ __device__ __forceinline__ void tick_body(const WorkItem* __restrict__ items, co
     s.v[V_HCLAIM] = 0;
     s.v[V_S4W] = 0;  // (s4_wave's "no candidates" mark: LDS outlives the previous item)
     s.v[V_S6W] = 0;
+    if constexpr (CLS) s.v[V_CLS] = 0;
     for (int q = 0; q < BS / 64; ++q) wtpl[q][0] = -1;
     if (fresh) {
       s.v[V_DEPTH0] = 0;
@@ -1963,8 +2008,11 @@ __device__ __forceinline__ void tick_body(const WorkItem* __restrict__ items, co
   const uint8_t* W = Z;  // identity when not filtering
   int ncand = 0, ntok = 0;
   bool s4_done = false;
-  const bool env_ready = (P.fast & 4) && filt && ndelta > 0 && Zn <= 2048 && ndelta <= 64 && emit;
-  if ((P.fast & 4) && filt && ndelta > 0 && Zn <= 2048 && ndelta <= 64) {  // the common tile: one wave (s4_wave)
+  // (a class tag set takes the block path below: s4_wave's matchers and its register-resident
+  // holdback test know literal patterns only, and stay exactly as they are for those)
+  const bool s4w = !CLS && (P.fast & 4) && filt && ndelta > 0 && Zn <= 2048 && ndelta <= 64;
+  const bool env_ready = s4w && emit;
+  if (s4w) {  // the common tile: one wave (s4_wave)
     if (tid >= 64 && env_ready) {
       // the idle waves: the item's envelope bytes, assembled off the fill's path
       const int b = tid - 64, ix = (int)it.index, p1 = P.pre1_len;
@@ -2061,6 +2109,14 @@ __device__ __forceinline__ void tick_body(const WorkItem* __restrict__ items, co
       for (int g = w; g * 16 < ncand; g += BS / 64) mfma_match_group(Z, Zn, s.cand, ncand, g, P, bf0, bf1, s.cand_tok);
     }
     __syncthreads();
+    if constexpr (CLS) {  // the shared walk, a candidate per thread
+      for (int c = tid; c < ncand; c += BS) {
+        const int r = class_token(Z, Zn, (int)s.cand[c], P, (int)s.cand_tok[c]);
+        if (r == kClsSuspect) s.v[V_CLS] = 1;
+        else s.cand_tok[c] = (int8_t)r;
+      }
+      __syncthreads();
+    }
     QMX_STAMP(6);
     if (ncand <= 64) {
       // common case (a few '<' in the tile): wave 0 alone compacts the tokens by ballot and
@@ -2150,11 +2206,11 @@ __device__ __forceinline__ void tick_body(const WorkItem* __restrict__ items, co
     // cuts per delta + new tail
     for (int j = tid; j < ndelta; j += BS) {
       int q;
-      s.cut[j] = (uint16_t)hold_cut(s, Z, ncand, ntok, s.dl_end[j], P, false, &q);
+      s.cut[j] = (uint16_t)hold_cut<CLS>(s, Z, ncand, ntok, s.dl_end[j], P, false, &q);
     }
     if (tid == 0) {
       int q;
-      hold_cut(s, Z, ncand, ntok, Zn, P, true, &q);
+      hold_cut<CLS>(s, Z, ncand, ntok, Zn, P, true, &q);
       s.v[V_NEWTAIL] = q;  // (V_NEWDEPTH: written with the depth scan above)
     }
     __syncthreads();
@@ -2291,9 +2347,11 @@ __device__ __forceinline__ void tick_body(const WorkItem* __restrict__ items, co
   QMX_STAMP(8);
   const int out_len = emit ? n_emit * EVL + etot : 0;
   const uint32_t new_clen = it.content_len + (uint32_t)Wlen;
-  if ((uint32_t)out_len > it.out_cap || new_clen > P.content_cap) {
+  // (class tags: an ambiguous window — decided here, before anything of the tile is published)
+  const bool cls_esc = CLS && s.v[V_CLS] != 0;
+  if ((uint32_t)out_len > it.out_cap || new_clen > P.content_cap || cls_esc) {
     if (tid == 0) {
-      WorkResult r{0u, 0u, (uint32_t)WS_ESCALATE, it.content_len};
+      WorkResult r{0u, 0u, (uint32_t)(WS_ESCALATE | (cls_esc ? WS_CLASS : 0)), it.content_len};
       res[bi] = r;
     }
     return;
@@ -2490,7 +2548,26 @@ struct FinShared {
   int32_t last_close[kMaxTags];  // start of the last close token of each tag in the text
   TagSet ts;                     // the tag set, staged from the kernel parameters
 };
-enum : int { FV_CUR = 0, FV_PEND, FV_SEGA, FV_NSEG, FV_NTOK, FV_S0, FV_S1, FV_NBIG, FV_OVF };
+enum : int { FV_CUR = 0, FV_PEND, FV_SEGA, FV_NSEG, FV_NTOK, FV_S0, FV_S1, FV_NBIG, FV_OVF,
+             FV_CLS,     // class tags: a suspect candidate, or a close that is not its open's captured text
+             FV_PPOS };  // class tags: where the pending open starts
+
+// match_at of a class tag set for K3 (strip tables: a dot takes a newline): the literal tags
+// by match_at, the class tags by the shared walk, the first in list order wins; kClsSuspect
+// when the candidate is suspect (qmx_text.h class_candidate).
+__device__ __forceinline__ int fin_class_token(const uint8_t* __restrict__ src, int n, int p, const TagSet& ts,
+                                               const TagClasses& tc, int* L) {
+  int lit_len = 0, tok = 0, len = 0;
+  const int lit = match_at(src, n, p, ts, &lit_len);
+  const int r = class_candidate(src, n, p, ts, tc, true, &tok, &len);
+  if (r == CC_SUSPECT) return kClsSuspect;
+  if (r == CC_MATCH && (lit == 0 || abs(tok) < abs(lit))) {
+    *L = len;
+    return tok;
+  }
+  *L = lit_len;
+  return lit;
+}
 
 // Interval selection of re.sub("<(t)>.*?</\1>", "", IGNORECASE|DOTALL): leftmost open whose
 // tag closes later (re tries every start position, so an open that never closes is just
@@ -2500,8 +2577,12 @@ enum : int { FV_CUR = 0, FV_PEND, FV_SEGA, FV_NSEG, FV_NTOK, FV_S0, FV_S1, FV_NB
 // one ballot + find-first + shuffle (no per-token thread-serial loop, no token-count cap).
 // Kept segments (text between selected intervals) go to segs[]; returns their count, -1 if
 // more than cap (host path).  Block-uniform.
+// Class tags (tc != null): the backreference compares a close with the text its open
+// captured, so the walk by tag id is exact only while every selected close equals that text
+// (ASCII case folded) and no candidate is suspect; otherwise -2 (host path, counted apart).
+template <bool CLS>
 __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n, const TagSet& ts, int2* __restrict__ segs, int cap,
-                          FinShared& F) {
+                          FinShared& F, const TagClasses* tc) {
   const int tid = threadIdx.x;
   if (tid < kMaxTags) F.last_close[tid] = -1;
   if (tid == 0) {
@@ -2510,12 +2591,23 @@ __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n
     F.v[FV_SEGA] = 0;
     F.v[FV_NSEG] = 0;
     F.v[FV_OVF] = 0;
+    if constexpr (CLS) F.v[FV_CLS] = F.v[FV_PPOS] = 0;
   }
+  auto tok_at = [&](int p, int* L) -> int {
+    if constexpr (!CLS) {
+      return match_at(src, n, p, ts, L);
+    } else {
+      const int id = fin_class_token(src, n, p, ts, *tc, L);
+      if (id != kClsSuspect) return id;
+      F.v[FV_CLS] = 1;
+      return 0;
+    }
+  };
   __syncthreads();
   for (int p = tid; p < n; p += BS) {  // pass 0: which opens can close at all
     if (src[p] != '<' || p + 1 >= n || src[p + 1] != '/') continue;
     int L = 0;
-    const int id = match_at(src, n, p, ts, &L);
+    const int id = tok_at(p, &L);
     if (id < 0) atomicMax(&F.last_close[-id - 1], p);
   }
   __syncthreads();
@@ -2528,14 +2620,14 @@ __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n
       for (int p = lo; p < hi; ++p) {
         if (src[p] != '<') continue;
         int L = 0;
-        cnt += match_at(src, n, p, ts, &L) != 0;
+        cnt += tok_at(p, &L) != 0;
       }
       int tot;
       int k = block_excl_sum(cnt, F.scr, &tot);
       for (int p = lo; p < hi && cnt > 0; ++p) {
         if (src[p] != '<') continue;
         int L = 0;
-        const int id = match_at(src, n, p, ts, &L);
+        const int id = tok_at(p, &L);
         if (id == 0) continue;
         F.tpos[k] = p;
         F.tkid[k] = (int8_t)id;
@@ -2562,6 +2654,12 @@ __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n
             m = __ballot(valid && id == -pend && pos >= cur);
             if (m == 0) break;
             const int L = __ffsll((unsigned long long)m) - 1;
+            if constexpr (CLS) {  // the close's name against the open's captured bytes, a byte per lane
+              wave_fence();  // (FV_PPOS: lane 0's store at the open, maybe a window ago)
+              const int ppos = F.v[FV_PPOS], cpos = __shfl(pos, L, 64), nl = ts.len[pend - 1];
+              const bool ne = lane < nl && lower_ascii(src[ppos + 1 + lane]) != lower_ascii(src[cpos + 2 + lane]);
+              if (__ballot(ne) != 0 && lane == 0) F.v[FV_CLS] = 1;
+            }
             cur = __shfl(end, L, 64);
             pend = 0;
             sega = cur;
@@ -2576,6 +2674,9 @@ __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n
             }
             pend = __shfl(id, L, 64);
             cur = __shfl(end, L, 64);
+            if constexpr (CLS) {
+              if (lane == 0) F.v[FV_PPOS] = po;
+            }
           }
         }
       }
@@ -2600,6 +2701,9 @@ __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n
   }
   __syncthreads();
   const int nseg = F.v[FV_NSEG];
+  if constexpr (CLS) {
+    if (F.v[FV_CLS] != 0) return -2;
+  }
   return nseg > cap ? -1 : nseg;
 }
 
@@ -2637,8 +2741,9 @@ __device__ __forceinline__ void fin_stage(const FinArgs& fa, int j, uint8_t* __r
   if (any) __syncthreads();  // (any is block-uniform)
 }
 
+template <bool CLS>
 __device__ __forceinline__ void fin_body(const FinArgs& fa, int j, const uint8_t* __restrict__ content, uint32_t content_cap,
-                         const TagSet& ts_mem, FinShared& F) {
+                         const TagSet& ts_mem, FinShared& F, const TagClasses* tc) {
   const int tid = opaque_tid();
   for (int i = tid; i < (int)(sizeof(TagSet) / 4); i += BS) ((uint32_t*)&F.ts)[i] = ((const uint32_t*)&ts_mem)[i];
   __syncthreads();
@@ -2666,9 +2771,12 @@ __device__ __forceinline__ void fin_body(const FinArgs& fa, int j, const uint8_t
     }
     int nseg = 1;
     if (strip) {
-      nseg = fin_select(src, n, ts, segs, (int)it.seg_cap, F);
+      nseg = fin_select<CLS>(src, n, ts, segs, (int)it.seg_cap, F, tc);
       if (nseg < 0) {
         bail();
+        if constexpr (CLS) {  // (status 3: the host path, for an ambiguous class tag)
+          if (nseg == -2 && tid == 0) fa.res[j].status = 3;
+        }
         return;
       }
     } else if (tid == 0) {
@@ -2826,6 +2934,7 @@ __device__ __forceinline__ FinArgs fin_uni(const FinArgs& a) {
 
 // One work item of a tick: k < n_tick a stream tile, else finalize request k - n_tick.
 // Publishes the item's result record last (fence + sequence number).
+template <bool CLS = false>
 __device__ __forceinline__ void run_item(int k, const WorkItem* __restrict__ items, const uint8_t* __restrict__ in,
                                          uint8_t* __restrict__ out, WorkResult* __restrict__ res,
                                          DevSlot* __restrict__ state, uint8_t* __restrict__ content,
@@ -2834,7 +2943,7 @@ __device__ __forceinline__ void run_item(int k, const WorkItem* __restrict__ ite
                                          TickLds& U) {
   const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
   if ((uint32_t)k < n_tick) {
-    tick_body(items, in, out, res, state, content, Pk, U.t, btpl_rd, btpl_wr, seq, k);
+    tick_body<CLS>(items, in, out, res, state, content, Pk, U.t, btpl_rd, btpl_wr, seq, k);
     if (threadIdx.x == 0) {
       res[k].t0 = t0;
       res[k].t1 = __builtin_amdgcn_s_memrealtime();
@@ -2850,7 +2959,7 @@ __device__ __forceinline__ void run_item(int k, const WorkItem* __restrict__ ite
     const int j = (int)(k - n_tick);
     const FinArgs fa = fin_uni(fa_src);
     fin_stage(fa, j, content, Pk.content_cap);
-    fin_body(fa, j, content, Pk.content_cap, Pk.ts, U.f);
+    fin_body<CLS>(fa, j, content, Pk.content_cap, Pk.ts, U.f, Pk.cls);
     if (threadIdx.x == 0) {
       fa.res[j].t0 = t0;
       fa.res[j].t1 = __builtin_amdgcn_s_memrealtime();
@@ -2872,6 +2981,19 @@ __global__ __launch_bounds__(BS) void qmx_tick_kernel(const WorkItem* __restrict
   // tag patterns, MFMA B operand and SSE envelopes: in device memory (uploaded by the lane
   // when they change, ~once a second), not a 1.5 KB by-value kernel argument per launch
   run_item((int)blockIdx.x, items, in, out, res, state, content, *Pkp, seq, n_tick, fa, btpl_rd, btpl_wr, U);
+}
+
+// The same launch for an engine with a class tag set (KParams::cls): the filter stage's
+// class walk, source-text holdback and ambiguity escalation, and K3's captured-text check.
+__global__ __launch_bounds__(BS) void qmx_ctick_kernel(const WorkItem* __restrict__ items,
+                                                       const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
+                                                       WorkResult* __restrict__ res, DevSlot* __restrict__ state,
+                                                       uint8_t* __restrict__ content, const KParams* __restrict__ Pkp,
+                                                       uint32_t seq, uint32_t n_tick, FinArgs fa,
+                                                       const BackendTpl* __restrict__ btpl_rd,
+                                                       BackendTpl* __restrict__ btpl_wr) {
+  __shared__ TickLds U;
+  run_item<true>((int)blockIdx.x, items, in, out, res, state, content, *Pkp, seq, n_tick, fa, btpl_rd, btpl_wr, U);
 }
 
 // ------------------------------------------------------------------------------------
@@ -3352,8 +3474,8 @@ void HipEngine::collect_timing(TickLane& L) {
 }
 
 HipEngine::HipEngine(const std::vector<std::string>& tags, int device, int tile_bytes, int max_slots,
-                     int content_cap, int lanes, HipGrid* grid, int door, int ndoors)
-    : HostEngine(tags),
+                     int content_cap, int lanes, HipGrid* grid, int door, int ndoors, bool classes)
+    : HostEngine(tags, classes),
       device_(device),
       tile_(std::min(std::max(tile_bytes, 1024), TILE_MAX) & ~15),
       max_slots_(max_slots),
@@ -3391,12 +3513,25 @@ HipEngine::HipEngine(const std::vector<std::string>& tags, int device, int tile_
     persistent_ = false;
     poll_ = true;
   }
+  if (tag_classes(ts_) != nullptr) {
+    // class tags: the persistent grids run the literal tag sets' kernel only (its registers
+    // are spoken for); a class tag set ticks with a launch per tick, on tick lanes
+    if (grid_) throw std::invalid_argument("class thinking tags run on tick lanes (tick_mode lanes), not on the loop-tick grid");
+    persistent_ = false;
+  }
   HIP_CHECK(hipMalloc(&d_state_, sizeof(DevSlot) * (size_t)max_slots_));
   HIP_CHECK(hipMemset(d_state_, 0, sizeof(DevSlot) * (size_t)max_slots_));
   HIP_CHECK(hipMalloc(&d_content_, (size_t)content_cap_ * (size_t)max_slots_));
 
   std::memset(&base_params_, 0, sizeof(base_params_));
   base_params_.ts = ts_;
+  if (const TagClasses* tc = tag_classes(ts_)) {
+    // class tags: the kernels read the class tables and the tags' source text from global
+    // memory, only where a class tag set needs them
+    HIP_CHECK(hipMalloc((void**)&d_cls_, sizeof(TagClasses)));
+    HIP_CHECK(hipMemcpy(d_cls_, tc, sizeof(TagClasses), hipMemcpyHostToDevice));
+    base_params_.cls = d_cls_;
+  }
   base_params_.npat = 2 * ts_.n;
   // matcher codes: every byte that occurs in a pattern gets its own code (letters: one code
   // for both cases, the tags' IGNORECASE), everything else shares code 95
@@ -3406,7 +3541,7 @@ HipEngine::HipEngine(const std::vector<std::string>& tags, int device, int tile_
     for (int p = 0; p < base_params_.npat; ++p)
       for (int j = 0; j < pattern_len(ts_, p); ++j) {
         const uint8_t b = pattern_byte(ts_, p, j);
-        if (base_params_.code[b] != 95) continue;
+        if (b >= 0x80 || base_params_.code[b] != 95) continue;  // (a class position is no byte)
         if (next > 94) throw std::invalid_argument("thinking tags use more than 94 distinct characters");
         base_params_.code[b] = (uint8_t)next;
         if (b >= 'a' && b <= 'z') base_params_.code[b - 32] = (uint8_t)next;
@@ -3529,6 +3664,7 @@ HipEngine::~HipEngine() {
   for (void* p : grave_dev_) hipFree(p);
   if (d_state_) hipFree(d_state_);
   if (d_content_) hipFree(d_content_);
+  if (d_cls_) hipFree(d_cls_);
 }
 
 // Arena growth while serving (the io loop's or lane's thread): timed, because a pinned
@@ -3570,7 +3706,7 @@ void HipEngine::set_persistent(bool on) {
       std::lock_guard<std::mutex> lg(L->mu);
       stop_persistent(*L);
     }
-  persistent_ = on;
+  persistent_ = on && d_cls_ == nullptr;  // (a class tag set: a launch per tick)
 }
 
 void HipEngine::debug_poison_results(int ahead) {
@@ -4040,8 +4176,9 @@ void HipEngine::post(HipJob& J) {
     L.p_last_post = steady_s();
     ++L.p_ticks;
   } else {
-    hipLaunchKernelGGL(qmx_tick_kernel, dim3(J.n + J.m), dim3(BS), 0, L.stream, B.h_items, B.h_in, J.arena->p,
-                       B.h_res, d_state_, d_content_, B.d_params, J.seq, (uint32_t)J.n, fa,
+    // (a class tag set: the kernel that carries the class paths, qmx_ctick_kernel)
+    hipLaunchKernelGGL(d_cls_ != nullptr ? qmx_ctick_kernel : qmx_tick_kernel, dim3(J.n + J.m), dim3(BS), 0, L.stream,
+                       B.h_items, B.h_in, J.arena->p, B.h_res, d_state_, d_content_, B.d_params, J.seq, (uint32_t)J.n, fa,
                        tpl + (size_t)(par ^ 1) * kBackendTpl, tpl + (size_t)par * kBackendTpl);
     HIP_CHECK(hipGetLastError());
   }
@@ -4093,6 +4230,7 @@ void HipEngine::complete(HipJob& J, std::vector<SlotResult>& results, std::vecto
     bool no_progress = (r.status & WS_ESCALATE) ||
                        (p.submitted == (size_t)tile_ && r.consumed == 0 && !(r.status & (WS_DONE | WS_ABORTED)));
     if (no_progress) {
+      if ((r.status & WS_ESCALATE) && (r.status & WS_CLASS)) ++class_escalations_;
       escalate(p.slot, w.fresh);
       keep_remainder(0);
       std::string all;
@@ -4476,6 +4614,7 @@ void HipEngine::collect_finalize(TickLane& L, const std::vector<const FinalizeRe
     const FinalizeReq& r = *gpu[i];
     const FinResult fr = L.h_finres[i];
     if (fr.status) {
+      if (fr.status & 2) ++class_fin_host_;
       finalize_host(r, out);
       continue;
     }
@@ -4580,6 +4719,9 @@ std::unordered_map<std::string, double> HipEngine::kernel_stats() {
   m["clk_cycles"] = cyc;  // summable across engines (/metrics sums the io loops' engines)
   m["clk_us"] = cus;
   m["escalations"] = (double)escalations_.load();
+  // class tags: streams / finalize requests the host path decided because a window was ambiguous
+  m["class_escalations"] = (double)class_escalations_.load();
+  m["class_fin_host"] = (double)class_fin_host_.load();
   m["requeues"] = (double)requeues_.load();  // WS_MORE: more events than a tile holds
   m["light_host_opens"] = (double)light_opens_.load();  // streams opened on the host path (latency mode)
   m["fin_host"] = (double)fin_host_.load();

@@ -503,7 +503,7 @@ std::atomic<uint64_t> c_verify_checked{0}, c_verify_mismatch{0};
 
 class Verifier {
  public:
-  explicit Verifier(const std::vector<std::string>& tags) : cpu_(tags) {}
+  Verifier(const std::vector<std::string>& tags, bool classes) : cpu_(tags, classes) {}
   void open(int slot, uint32_t gen, int index, bool f, bool e) {
     std::lock_guard<std::mutex> g(mu_);
     Track t;
@@ -685,7 +685,8 @@ class GpuHub {
   GpuHub(const ServerCfg& cfg, int nloops) : cfg_(cfg), sinks_(nloops), pools_(nloops) {
     lanes_ = std::max(1, std::min(cfg.tick_lanes, 8));
     if (cfg.engine == "hip") {
-      HipEngine* he = new HipEngine(cfg.tags, cfg.device, cfg.tile, cfg.max_slots, cfg.content_cap, lanes_);
+      HipEngine* he = new HipEngine(cfg.tags, cfg.device, cfg.tile, cfg.max_slots, cfg.content_cap, lanes_, nullptr, -1,
+                                     1, cfg.tag_classes);
       he->set_remote_hbm_direct(remote_hbm_direct(cfg));
       // (spread placement: an RCCL round writes a remote final text into the content arena
       // and its stream is synchronised before the text is applied; the finalize that reads it
@@ -693,8 +694,8 @@ class GpuHub {
       // persistent grids alike)
       eng_.reset(he);
     } else
-      eng_.reset(new CpuEngine(cfg.tags));  // shared CPU engine: exercises the hub routing on CPU
-    if (cfg.verify) ver_.reset(new Verifier(cfg.tags));
+      eng_.reset(new CpuEngine(cfg.tags, cfg.tag_classes));  // shared CPU engine: exercises the hub routing on CPU
+    if (cfg.verify) ver_.reset(new Verifier(cfg.tags, cfg.tag_classes));
   }
   ~GpuHub() {
     {
@@ -1256,7 +1257,7 @@ class Loop {
         prctl(PR_SET_TIMERSLACK, 1000UL, 0, 0, 0);  // 1 us: the tick polls sleep a few us
         const int per = std::max(128, cfg_.max_slots / std::max(1, cfg_.threads));
         heng_ = new HipEngine(cfg_.tags, cfg_.device, cfg_.tile, per, cfg_.content_cap, 1, grid_,
-                              idx_ * loop_doors_, loop_doors_);
+                              idx_ * loop_doors_, loop_doors_, cfg_.tag_classes);
         heng_->set_remote_hbm_direct(remote_hbm_direct(cfg_));
         eng_.reset(heng_);
         aeng_ = heng_;
@@ -1264,12 +1265,12 @@ class Loop {
       } else if (cfg_.tick_mode == "loops") {
         // the loop-tick protocol on the CPU: jobs run on the engine's worker thread while the
         // loop polls for them (tests / TSan of the io loops' asynchronous tick path)
-        aeng_ = new AsyncCpuEngine(cfg_.tags);
+        aeng_ = new AsyncCpuEngine(cfg_.tags, cfg_.tag_classes);
         eng_.reset(aeng_);
       } else {
-        eng_.reset(new CpuEngine(cfg_.tags));
+        eng_.reset(new CpuEngine(cfg_.tags, cfg_.tag_classes));
       }
-      if (cfg_.verify) ver_.reset(new Verifier(cfg_.tags));
+      if (cfg_.verify) ver_.reset(new Verifier(cfg_.tags, cfg_.tag_classes));
     }
   }
 
@@ -3515,7 +3516,7 @@ class Loop {
     const char* e = env_get("QMX_LOOP_REQ_CHECK");
     return !e || atoi(e) != 0;
   }();
-  TagSet ts_ = make_tagset(cfg_.tags);
+  TagSet ts_ = make_tagset(cfg_.tags, cfg_.tag_classes);
   bool kick_ = false;
   std::mutex rmu_;
   std::vector<ResultBatch> rq_;
@@ -3710,7 +3711,9 @@ int run_server(const ServerCfg& cfg0) {
   // (rehearsals) split the grid budget: HipGrid sizes itself from QMX_GPU_SHARERS, and a grid
   // that does not fit falls back to lanes below.
   (void)spread;
-  const bool loop_ticks = hip && cfg.tick_mode != "lanes" && cfg.shared_engine != 1;
+  // (a class tag set, runtime.native_regex_tags: tick lanes — the grid runs the literal kernel)
+  const bool cls_tags = cfg.tag_classes && tag_classes(make_tagset(cfg.tags, true)) != nullptr;
+  const bool loop_ticks = hip && cfg.tick_mode != "lanes" && cfg.shared_engine != 1 && !cls_tags;
   const bool shared = !loop_ticks && (cfg.shared_engine < 0 ? hip : cfg.shared_engine > 0);
   if (shared) hub.reset(new GpuHub(cfg, (int)loops.size()));
   if (loop_ticks) {

@@ -34,11 +34,32 @@ constexpr int kJsonMaxDepth = 256;  // deeper == RecursionError (stream abort)
 // ---------------------------------------------------------------------------
 // tag patterns
 // ---------------------------------------------------------------------------
+// Class tags (make_tagset(tags, classes = true)): the fixed-width part of the regex language
+// the reference's alternation speaks — '.', bracket classes and escaped punctuation.  A tag is
+// then a sequence of elements that match one code point each; name[] keeps a literal element
+// as its lowercase byte and a class element as 0x80 + its index into TagClasses (pattern bytes
+// are otherwise printable ASCII), len[] counts elements.
+constexpr int kMaxClasses = 32;
+enum : uint8_t { CLS_WIDE = 1, CLS_DOT = 2 };  // accepts non-ASCII code points / is a '.'
+struct TagClasses {
+  int n;                               // distinct class definitions
+  uint32_t tab[kMaxClasses][4];        // ASCII acceptance under IGNORECASE | DOTALL (bit b of the 128)
+  uint8_t flags[kMaxClasses];
+  int srclen[kMaxTags];
+  uint8_t src[kMaxTags][kMaxTagLen + 1];  // the tag's lowercased source text (depth-0 holdback)
+};
+
+// (The layout of TagSet is the literal tag sets': the kernels keep a copy in LDS.  A class
+// tag set is marked in the one spare byte of name[0] — a tag is at most kMaxTagLen bytes —
+// with the id of its TagClasses: host code finds them with tag_classes(), qmx_engine.h, the
+// kernels get a pointer to their device copy in KParams.)
 struct TagSet {
   int n;                                   // distinct lowercase tags
   int len[kMaxTags];
-  uint8_t name[kMaxTags][kMaxTagLen + 1];  // lowercase ASCII
+  uint8_t name[kMaxTags][kMaxTagLen + 1];  // lowercase ASCII (class tags: see TagClasses)
 };
+// 0: a literal tag set; else some tag has a class element or an escape
+QMX_HD int tagset_cls_id(const TagSet& ts) { return ts.name[0][kMaxTagLen]; }
 
 QMX_HD uint8_t lower_ascii(uint8_t c) { return (c >= 'A' && c <= 'Z') ? (uint8_t)(c + 32) : c; }
 
@@ -86,6 +107,141 @@ QMX_HD bool pattern_prefix(const R& x, int q, int n, const TagSet& ts, bool open
     if (m > P) continue;
     bool ok = true;
     for (int i = 0; ok && i < m; ++i) ok = lower_ascii(x[q + i]) == pattern_byte(ts, pat, i);
+    if (ok) return true;
+  }
+  return false;
+}
+
+// ---------------------------------------------------------------------------
+// class tags: one code point per element (tagset_cls_id(ts) != 0; tc: the set's TagClasses)
+// ---------------------------------------------------------------------------
+// Does class element `k` accept the ASCII byte c?  The streaming filter's regex has no DOTALL
+// (a dot rejects '\n' there); the final strip's has.
+QMX_HD bool class_accepts(const TagClasses& tc, int k, uint8_t c, bool strip) {
+  if (c == '\n' && (tc.flags[k] & CLS_DOT)) return strip;
+  return (tc.tab[k][c >> 5] >> (c & 31)) & 1u;
+}
+
+// Walk pattern `pat` (pat < n: "<t>", else "</t>") over x[p:n).  1: it matches, *end is the
+// index after its '>';  0: mismatch;  -1: every byte of x[p:n) matched and the text ended
+// before the pattern did (a proper prefix — a code point cut short at n counts as one).
+template <class R>
+QMX_HD int class_walk(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, int pat, bool strip,
+                      int* end) {
+  const bool close = pat >= ts.n;
+  const int t = close ? pat - ts.n : pat;
+  int s = p;
+  if (s >= n) return -1;
+  if (x[s] != '<') return 0;
+  ++s;
+  if (close) {
+    if (s >= n) return -1;
+    if (x[s] != '/') return 0;
+    ++s;
+  }
+  for (int i = 0; i < ts.len[t]; ++i) {
+    if (s >= n) return -1;
+    const uint8_t c = x[s], e = ts.name[t][i];
+    if (e < 0x80) {
+      if (lower_ascii(c) != e) return 0;
+      ++s;
+    } else if (c < 0x80) {
+      if (!class_accepts(tc, e - 0x80, c, strip)) return 0;
+      ++s;
+    } else {
+      if (!(tc.flags[e - 0x80] & CLS_WIDE)) return 0;
+      const int ln = c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : c >= 0xC0 ? 2 : 1;
+      if (s + ln > n) return -1;
+      s += ln;
+    }
+  }
+  if (s >= n) return -1;
+  if (x[s] != '>') return 0;
+  *end = s + 1;
+  return 1;
+}
+
+// match_at for a class tag set: the open of every tag in list order, then (x[p+1] == '/':
+// the first element of a tag is a literal, never '/') the close of every tag.
+template <class R>
+QMX_HD int class_match_at(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, bool strip,
+                          int* tok_len) {
+  if (x[p] != '<') return 0;
+  const bool close = (p + 1 < n && x[p + 1] == '/');
+  for (int t = 0; t < ts.n; ++t) {
+    int end = 0;
+    if (class_walk(x, n, p, ts, tc, close ? ts.n + t : t, strip, &end) == 1) {
+      *tok_len = end - p;
+      return close ? -(t + 1) : (t + 1);
+    }
+  }
+  return 0;
+}
+
+// The suspect rule of the GPU kernels, which keep their token model (one pattern per '<',
+// fixed byte length, no overlapping tokens) by deciding only unambiguous windows: the
+// candidate '<' at p against the open (x[p+1] == '/': the close) of every tag that has a class
+// element, pattern positions in order.  A literal mismatch or a byte outside a class's table
+// rejects that tag; a '<', '>' or non-ASCII byte AT a class position makes the candidate
+// suspect — a class may swallow it, so token lengths and starts are no longer fixed, and the
+// exact host path decides the stream.  CC_MATCH: the first tag in list order that matches,
+// every class position one ASCII byte (*tok, *tok_len as match_at).  Text that ends before a
+// pattern does is no match here (the holdback's prefix tests look at it).
+enum : int { CC_NONE = 0, CC_MATCH = 1, CC_SUSPECT = 2 };
+template <class R>
+QMX_HD int class_candidate(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, bool strip, int* tok,
+                           int* tok_len) {
+  const bool close = p + 1 < n && x[p + 1] == '/';
+  const int s0 = p + (close ? 2 : 1);
+  int res = CC_NONE;
+  for (int t = 0; t < ts.n; ++t) {
+    const int L = ts.len[t];
+    bool has = false;
+      for (int i = 0; i < L; ++i) has = has || ts.name[t][i] >= 0x80;
+    if (!has) continue;
+    bool ok = true;
+      for (int i = 0; ok && i < L; ++i) {
+      if (s0 + i >= n) {
+        ok = false;
+        break;
+      }
+      const uint8_t c = x[s0 + i], e = ts.name[t][i];
+      if (e < 0x80) ok = lower_ascii(c) == e;
+      else if (c == '<' || c == '>' || c >= 0x80) return CC_SUSPECT;
+      else ok = class_accepts(tc, e - 0x80, c, strip);
+    }
+    if (ok && res == CC_NONE && s0 + L < n && x[s0 + L] == '>') {
+      res = CC_MATCH;
+      *tok = close ? -(t + 1) : (t + 1);
+      *tok_len = s0 + L + 1 - p;
+    }
+  }
+  return res;
+}
+
+// Is x[q:n) a proper class-aware prefix of some open or close pattern (streaming tables)?
+template <class R>
+QMX_HD bool class_prefix(const R& x, int q, int n, const TagSet& ts, const TagClasses& tc) {
+  for (int pat = 0; pat < 2 * ts.n; ++pat) {
+    int end = 0;
+    if (class_walk(x, n, q, ts, tc, pat, false, &end) == -1) return true;
+  }
+  return false;
+}
+
+// Is x[q:n), ASCII-lowercased, a prefix of the source text "<" + tag + ">" of some tag?  The
+// reference's depth-0 holdback is `startswith` on the source, not a pattern test.
+template <class R>
+QMX_HD bool source_prefix(const R& x, int q, int n, const TagSet& ts, const TagClasses& tc) {
+  const int m = n - q;
+  for (int t = 0; t < ts.n; ++t) {
+    const int L = tc.srclen[t];
+    if (m > L + 2) continue;
+    bool ok = true;
+      for (int i = 0; ok && i < m; ++i) {
+      const uint8_t want = i == 0 ? (uint8_t)'<' : i <= L ? tc.src[t][i - 1] : (uint8_t)'>';
+      ok = lower_ascii(x[q + i]) == want;
+    }
     if (ok) return true;
   }
   return false;

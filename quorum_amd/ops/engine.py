@@ -60,14 +60,24 @@ _PLAIN_TAG = re.compile(r"^[ -~]+$")
 _NOT_PLAIN = set(".^$*+?{}[]\\|()<>/")
 
 
-def native_tag_ok(tags: Sequence[str], max_tags: int = 16, max_len: int = 61) -> bool:
+def native_tag_ok(tags: Sequence[str], max_tags: int = 16, max_len: int = 61, classes: bool = False) -> bool:
     """Tags the native/GPU matchers run exactly (qmx_text.h): literal printable ASCII, at
     most 16 distinct (lowercased) tags of at most 61 bytes — the MFMA matcher compares a
     16-byte window per '<' and the tail of longer patterns, two 16-pattern column blocks.
-    Anything else runs on the python engine with real regex semantics."""
+    Anything else runs on the python engine with real regex semantics.
+
+    ``classes`` (``runtime.native_regex_tags``): also the class tags — '.', bracket classes
+    and escaped punctuation after a literal first element.  The C++ parser (``make_tagset``)
+    is the one definition of that subset, so it is asked."""
     low = {t.lower() for t in tags}
-    return (0 < len(low) <= max_tags
-            and all(_PLAIN_TAG.match(t) and not (set(t) & _NOT_PLAIN) and len(t) <= max_len for t in low))
+    if (0 < len(low) <= max_tags
+            and all(_PLAIN_TAG.match(t) and not (set(t) & _NOT_PLAIN) and len(t) <= max_len for t in low)):
+        return True
+    if not classes or max_tags != 16 or max_len != 61:
+        return False
+    from . import native
+
+    return native.available() and bool(native.require().tagset_ok([str(t) for t in tags], True))
 
 
 class PyEngine:
@@ -155,7 +165,7 @@ class PyEngine:
         return {"engine": self.name, "slots": len(self._slots)}
 
 
-_NATIVE_CACHE: Dict[Tuple[str, Tuple[str, ...], int], object] = {}
+_NATIVE_CACHE: Dict[Tuple[object, Tuple[str, ...], int], object] = {}
 
 
 def _py_engine(tags: Sequence[str]) -> PyEngine:
@@ -174,8 +184,9 @@ def make_engine(kind: str, tags: Sequence[str], device: Optional[int] = None, **
     extension or a GPU is missing (no silent fallback on a GPU box).
     """
     tags = list(tags)
-    if kind == "python" or not native_tag_ok(tags):
-        if kind in ("hip", "cpu") and not native_tag_ok(tags):
+    classes = bool(opts.pop("classes", False))
+    if kind == "python" or not native_tag_ok(tags, classes=classes):
+        if kind in ("hip", "cpu") and not native_tag_ok(tags, classes=classes):
             logger.warning("thinking_tags %r need regex semantics: using the python engine", tags)
         return _py_engine(tags)
     from . import native  # noqa: WPS433 - heavy import deferred
@@ -185,10 +196,12 @@ def make_engine(kind: str, tags: Sequence[str], device: Optional[int] = None, **
             logger.warning("native extension not built: using the python engine")
             return _py_engine(tags)
         kind = "hip" if native.gpu_available() else "cpu"
-    key = (kind, tuple(t.lower() for t in tags), -1 if device is None else device)
+    # (class tags keep their case in the key: "[Z-a]" and "[z-a]" are different patterns)
+    key = ((kind, classes) if classes else kind, tuple(t if classes else t.lower() for t in tags),
+           -1 if device is None else device)
     eng = _NATIVE_CACHE.get(key)
     if eng is None:
-        eng = native.NativeEngine(kind, tags, device=device, **opts)
+        eng = native.NativeEngine(kind, tags, device=device, classes=classes, **opts)
         _NATIVE_CACHE[key] = eng
     return eng
 

@@ -51,9 +51,10 @@ def gpu_available() -> bool:
         return False
 
 
-def strip_fn(tags: Sequence[str]) -> Callable[[str, bool], str]:
+def strip_fn(tags: Sequence[str], classes: bool = False) -> Callable[[str, bool], str]:
     ext = require()
-    stripper = ext.Stripper([t.lower() for t in tags])
+    # class tags go down as written: lowercasing would turn "[Z-a]" into another pattern
+    stripper = ext.Stripper(list(tags), classes=True) if classes else ext.Stripper([t.lower() for t in tags])
 
     def _strip(text, on):
         if not on:
@@ -70,14 +71,16 @@ class NativeEngine:
 
     def __init__(self, kind: str, tags: Sequence[str], device: Optional[int] = None,
                  tile_bytes: int = 16384, max_slots: int = 8192, content_cap: int = 1 << 20, lanes: int = 1,
-                 grid=None, door: int = -1, ndoors: int = 1):
+                 grid=None, door: int = -1, ndoors: int = 1, classes: bool = False):
         ext = require()
         self.kind = kind
         self.name = kind
         self.tags: List[str] = list(tags)
+        self.classes = bool(classes)
         low = []
         for t in tags:
-            t = t.lower()
+            # class tags go down as written: lowercasing would turn "[Z-a]" into another pattern
+            t = t if classes else t.lower()
             if t not in low:
                 low.append(t)
         if kind == "hip":
@@ -86,10 +89,11 @@ class NativeEngine:
             if device is None:
                 device = int(os.environ.get("LOCAL_RANK", "0")) % max(ext.device_count(), 1)
             # grid: a HipGrid (loop ticks) — this engine posts its ticks into door `door` of it
-            self._e = ext.HipEngine(low, device, tile_bytes, max_slots, content_cap, lanes, grid, door, ndoors)
+            self._e = ext.HipEngine(low, device, tile_bytes, max_slots, content_cap, lanes, grid, door, ndoors,
+                                     classes=self.classes)
             self.offload = True
         else:
-            self._e = ext.CpuEngine(low)
+            self._e = ext.CpuEngine(low, classes=self.classes)
             self.offload = False
         self.open = self._e.open
         self.feed = self._e.feed

@@ -4,7 +4,9 @@
 // Properties checked on random inputs (no python in the loop):
 //  * streaming invariance: the C++ CPU engine produces byte-identical SSE output, flags,
 //    content and finals whether a stream is fed in one piece or split at random points with
-//    ticks at random moments (the tile/carry/holdback logic of every split point);
+//    ticks at random moments (the tile/carry/holdback logic of every split point) — with the
+//    default tags and with class tag sets ('.', "[...]", escapes: make_tagset(tags, true)),
+//    their pieces including multi-byte code points and '<' / '>' at class positions;
 //  * strip_final idempotence on already-stripped text and JSON DOM round-trips
 //    (parse(dump(parse(x))) == parse(x)), py_float_repr/escape on random inputs;
 //  * everything runs under -fsanitize=address,undefined: any OOB / UB aborts the run.
@@ -31,10 +33,30 @@ const char* kPieces[] = {"<think>", "</think>", "<THINK>", "</Think>", "<reason>
                          "<", ">", "x", "hello ", " ", "\n", "\\n", "\\\"", "\\\\", "\\u00e9", "\\ud83d\\ude00",
                          "\xc3\xa9", "\xe4\xb8\xad", "\xf0\x9f\x98\x80", "\\u0000", "\t", "0"};
 
+// class tag sets and pieces that instantiate them (JSON string bodies, as kPieces)
+struct ClassSet {
+  std::vector<std::string> tags;
+  std::vector<const char*> pieces;
+};
+const ClassSet kClassSets[] = {
+    {{"think", "th.nk"},
+     {"<thXnk>", "</th-nk>", "<TH.NK>", "<th", "Xnk>", ".nk>", "</th", "<th\xe4\xb8\xadnk>", "</th\\u4e2dnk>",
+      "<th\xf0\x9f\x98\x80nk>", "<th\\ud83d\\ude00nk>", "<th<nk>", "<th>nk>", "<th\\nnk>", "</thXnk>", "<think>", "</think>"}},
+    {{"t[0-9][0-9]", "note\\.x", "n[a-c-]te", "x[^y]z"},
+     {"<t42>", "</T07>", "<t4", "2>", "<tx2>", "<note.x>", "</NOTE.X>", "<noteQx>", "<note\\\\.", "x>", "<n-te>", "</nBte>",
+      "<ndte>", "<xQz>", "</x\xc3\xa9z>", "<x<z>", "<x>z>", "<xyz>", "<x\\nz>", "</x", "z>"}},
+    {{"a.", "a", "q[^a-z]"},
+     {"<a>", "<a>>", "</a>>", "</a>", "<aX>", "</A\xe4\xb8\xad>", "<q1>", "</q\xf0\x9f\x98\x80>", "<qa>", "<q<>", "<q", "<a"}},
+};
+const ClassSet* g_class = nullptr;  // the class tag set of this iteration (null: the default tags)
+
 std::string rand_content() {
   std::string s;
   int n = R(12);
-  for (int i = 0; i < n; ++i) s += kPieces[R(sizeof(kPieces) / sizeof(kPieces[0]))];
+  for (int i = 0; i < n; ++i) {
+    if (g_class != nullptr && R(2)) s += g_class->pieces[R((int)g_class->pieces.size())];
+    else s += kPieces[R(sizeof(kPieces) / sizeof(kPieces[0]))];
+  }
   return s;
 }
 
@@ -66,7 +88,7 @@ struct Run {
 
 Run run_engine(const std::vector<std::string>& tags, const std::vector<std::string>& bodies,
                const std::vector<bool>& filt, bool split) {
-  CpuEngine eng(tags);
+  CpuEngine eng(tags, g_class != nullptr);
   Run out;
   std::vector<int> slots;
   for (size_t i = 0; i < bodies.size(); ++i) slots.push_back(eng.open((int)i, filt[i], true));
@@ -157,9 +179,12 @@ std::string rand_json(int depth = 0) {
 int main(int argc, char** argv) {
   int iters = argc > 1 ? atoi(argv[1]) : 300;
   rng.seed(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
-  const std::vector<std::string> tags = {"think", "reason", "reasoning", "thought"};
+  const std::vector<std::string> default_tags = {"think", "reason", "reasoning", "thought"};
   int fails = 0;
   for (int it = 0; it < iters; ++it) {
+    // every other iteration: one of the class tag sets
+    g_class = it % 2 ? &kClassSets[(it / 2) % (int)(sizeof(kClassSets) / sizeof(kClassSets[0]))] : nullptr;
+    const std::vector<std::string>& tags = g_class ? g_class->tags : default_tags;
     int ns = 1 + R(4);
     std::vector<std::string> bodies;
     std::vector<bool> filt;
@@ -177,7 +202,7 @@ int main(int argc, char** argv) {
       if (++fails <= 3) fprintf(stderr, "streaming invariance violated (iteration %d)\n", it);
     }
     // strip_final: stripping a stripped text (no tags left in it) only re-strips whitespace
-    TagSet ts = make_tagset(tags);
+    TagSet ts = make_tagset(tags, g_class != nullptr);
     std::string t = rand_content() + rand_content();
     std::string s1 = strip_final(ts, (const uint8_t*)t.data(), t.size());
     std::string s2 = strip_final(ts, (const uint8_t*)s1.data(), s1.size());

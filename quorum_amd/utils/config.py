@@ -281,6 +281,12 @@ class RuntimeConfig:
                TTFT 0.040 -> 0.018 ms at one connection, neutral at the headline's load
                (profiles/r6/lowload/light_host).  0: off; unset: QMX_LIGHT_HOST, which `serve`
                sets to 2 for its workers and bench.py to 0
+    native_regex_tags: run class thinking tags — '.', bracket classes "[...]" and escaped
+               punctuation after a literal first character, e.g. "th.nk" or "t[0-9]" — on the
+               native engines with the reference's regex semantics.  Off (the default): any
+               tag with a regex metacharacter sends the streams to the python engine and
+               keeps the native server from starting.  Tags outside that subset (quantifiers,
+               groups, anchors, "|", shorthands) are refused either way
     """
 
     engine: str = "auto"
@@ -304,6 +310,11 @@ class RuntimeConfig:
     watch_interval: float = 1.0
     read_pace_us: int = 50
     light_host_sessions: Optional[int] = None
+    native_regex_tags: bool = False
+
+    def __post_init__(self):
+        if not isinstance(self.native_regex_tags, bool):
+            raise ValueError(f"runtime.native_regex_tags must be true or false, got {self.native_regex_tags!r}")
 
     @classmethod
     def from_config(cls, cfg: Dict[str, Any]) -> "RuntimeConfig":

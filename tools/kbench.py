@@ -62,11 +62,15 @@ def main():
                     help="mock: the benchmark's upstream stream; tagdense: '<'-heavy content (MFMA matcher load)")
     ap.add_argument("--events-per-tick", type=int, default=0,
                     help="stream the body N events per tick (steady-state serving shape); 0 = whole body in one tick")
+    ap.add_argument("--tags", default="think,reason,reasoning,thought", help="comma-separated thinking tags")
+    ap.add_argument("--classes", action="store_true",
+                    help="class tags ('.', '[...]': runtime.native_regex_tags), e.g. --tags think,th.nk; one-shot "
+                         "launches only (a class tag set does not run on the persistent grid)")
     args = ap.parse_args()
     from quorum_amd.ops.native import NativeEngine
 
     body = mock_stream() if args.shape == "mock" else tagdense_stream()
-    tags = ["think", "reason", "reasoning", "thought"]
+    tags = args.tags.split(",")
     results = []
     grid = None
     if args.grid > 0:
@@ -77,6 +81,8 @@ def main():
     for filt, emit in [combos[c] for c in args.combos.split(",")]:
         for n in [int(x) for x in args.slots.split(",")]:
             kw = {"grid": grid, "door": 0} if grid is not None else {}
+            if args.classes:
+                kw["classes"] = True
             eng = NativeEngine(args.engine, tags, device=0, max_slots=4096, content_cap=1 << 16, **kw)
             walls = []
             evs = [e + b"\n\n" for e in body.split(b"\n\n") if e]
@@ -96,7 +102,7 @@ def main():
                     eng.release(s)
             st = eng._e.kernel_stats() if args.engine == "hip" else {}
             walls.sort()
-            rec = {"filter": filt, "emit": emit, "shape": args.shape, "slots": n, "bytes_per_slot": len(body),
+            rec = {"filter": filt, "emit": emit, "shape": args.shape, "tags": tags, "slots": n, "bytes_per_slot": len(body),
                    "events_per_tick": k,
                    "wall_us_p50": round(1e6 * walls[len(walls) // 2], 1),
                    "wall_us_min": round(1e6 * walls[0], 1)}
