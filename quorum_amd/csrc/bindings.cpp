@@ -490,6 +490,11 @@ PYBIND11_MODULE(_qmx, m) {
       return false;
     }
   }, py::arg("tags"), py::arg("classes") = false);
+  // does this tag list make a class tag set (a '.', a bracket class)?  The test HipEngine uses
+  // to pair an engine with a grid: a class tag set needs HipGrid(classes=True)
+  m.def("tagset_has_classes", [](const std::vector<std::string>& tags, bool classes) {
+    return tag_classes(make_tagset(tags, classes)) != nullptr;
+  }, py::arg("tags"), py::arg("classes") = true);
   // candidates '<' of `text` the GPU kernels would hand to the host path (qmx_text.h
   // class_candidate, the shared suspect rule), with the streaming or the strip tables
   m.def("class_suspects", [](const std::vector<std::string>& tags, const std::string& text, bool strip) {
@@ -514,11 +519,13 @@ PYBIND11_MODULE(_qmx, m) {
   bind_engine(ce);
   // the multi-door grid of loop ticks (tests drive several door engines from Python threads)
   py::class_<HipGrid>(m, "HipGrid")
-      .def(py::init([](int device, int doors, int wg_per_door, int idle_ms) {
+      // (classes: the grid of a class tag set — its doors take engines with a class tag set only)
+      .def(py::init([](int device, int doors, int wg_per_door, int idle_ms, bool classes) {
              env_refresh();
-             return new HipGrid(device, doors, wg_per_door, idle_ms);
+             return new HipGrid(device, doors, wg_per_door, idle_ms, classes);
            }),
-           py::arg("device"), py::arg("doors"), py::arg("wg_per_door") = 8, py::arg("idle_ms") = 50)
+           py::arg("device"), py::arg("doors"), py::arg("wg_per_door") = 8, py::arg("idle_ms") = 50,
+           py::arg("classes") = false)
       .def("housekeep", &HipGrid::housekeep)
       .def("stop", &HipGrid::stop, py::call_guard<py::gil_scoped_release>())
       .def("stats", &HipGrid::stats);

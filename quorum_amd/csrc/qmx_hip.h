@@ -168,9 +168,13 @@ struct PCtl;   // persistent mode: device control block
 // process), so every wave reaches an exit even if the host never stops the grid.
 class HipGrid {
  public:
-  HipGrid(int device, int doors, int wg_per_door, int idle_ms);
+  // classes: the grid of a class tag set — it launches qmx_ctick_persistent (the class paths),
+  // one workgroup per CU whatever QMX_GRID_OCC says; its doors take engines with a class tag
+  // set only, as a literal grid's doors take literal tag sets only
+  HipGrid(int device, int doors, int wg_per_door, int idle_ms, bool classes = false);
   ~HipGrid();
   int doors() const { return n_; }
+  bool classes() const { return classes_; }
   PDoor* door(int d) const;
   // held by a door's owner while it writes and posts a tick
   std::shared_lock<std::shared_mutex> post_guard();
@@ -192,6 +196,7 @@ class HipGrid {
   std::atomic<double> clk_off_us_{__builtin_nan("")};
   bool interleave_ = true;  // doors' sub-grids XCD-local (blocks d, d + doors, ...)
   int occ_ = 1;             // workgroups per CU the kernel variant allows (QMX_GRID_OCC)
+  const bool classes_;      // the class tag sets' kernel (always one workgroup per CU)
   // written by calibrate_locked (exclusive lock); read lock-free by housekeep() / stats()
   std::atomic<double> clk_rtt_us_{0.0}, last_cal_{0.0};
   int device_, n_, wpd_, idle_ms_;

@@ -452,9 +452,10 @@ __device__ inline bool pattern_prefix_w(const uint8_t* Z, int q, int e, const KP
 // ------------------------------------------------------------------------------------
 // class tags (KParams::cls != null)
 // ------------------------------------------------------------------------------------
-// Everything a class tag set adds is compiled under `CLS`, into a kernel of its own
-// (qmx_ctick_kernel): the literal tag sets' kernels are the code they were, registers and
-// all (tests/test_isa.py), and an engine with a class tag set launches the other one.
+// Everything a class tag set adds is compiled under `CLS`, into kernels of its own
+// (qmx_ctick_kernel, the launch per tick, and qmx_ctick_persistent, the loop-tick grid): the
+// literal tag sets' kernels are the code they were, registers and all (tests/test_isa.py),
+// and an engine with a class tag set launches, or posts into a grid of, the other ones.
 // The fast matchers compare bytes for equality, and a class position of a pattern holds
 // 0x80 + class index — no byte of a window that is not suspect — so they keep matching the
 // literal tags and the class tags come from the shared walk (qmx_text.h class_candidate), one
@@ -3062,13 +3063,17 @@ static_assert(offsetof(PDoor, beat) == offsetof(PDoor, posted) + 4, "posted + be
 // loads: a readonly noalias kernel argument may be read through the scalar cache, which no
 // acquire fence invalidates — the next tick's descriptor would come back stale.
 //
-// WPE: waves per SIMD the register allocation must allow.  2 (the default): one 512-thread
+// WPE (the kernels below): waves per SIMD the register allocation must allow.  2 (the default): one 512-thread
 // workgroup per CU (8 waves on 4 SIMDs), up to 256 VGPRs.  4: two workgroups per CU — at most
 // 128 VGPRs (some live values go to scratch) and 2 x 79 KB of the CU's 160 KB LDS; the grid
 // then counts its budget in workgroup slots (HipGrid, QMX_GRID_OCC=2).
-template <int WPE>
-__global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void qmx_tick_persistent(
-    PDoor* doors, PCtl* ctls, int wpd, uint32_t gen, uint32_t idle_ticks, int interleave) {
+//
+// CLS: the items run with the class paths (run_item<true>, a class tag set's KParams::cls).
+// The relay / claim / item loop is this one body for every persistent kernel; the kernels
+// below differ in CLS and in the register allocation they ask for.
+template <bool CLS>
+__device__ __forceinline__ void persistent_body(PDoor* doors, PCtl* ctls, int wpd, uint32_t gen, uint32_t idle_ticks,
+                                                int interleave) {
   __shared__ TickLds U;
   __shared__ TickDesc D;
   __shared__ uint32_t cmd;  // new tick's sequence number, 0: exit
@@ -3227,12 +3232,25 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       // launch-invariant data (which the compiler does for uniform addresses it proves
       // unclobbered within the kernel)
       asm volatile("" ::: "memory");
-      run_item(k, uni(D.items), uni(D.in), uni(D.out), uni(D.res), uni(D.state), uni(D.content), *uni(D.params), seq,
-               n_tick, D.fa, uni(D.btpl_rd), uni(D.btpl_wr), U);
+      run_item<CLS>(k, uni(D.items), uni(D.in), uni(D.out), uni(D.res), uni(D.state), uni(D.content), *uni(D.params),
+                    seq, n_tick, D.fa, uni(D.btpl_rd), uni(D.btpl_wr), U);
       __syncthreads();  // LDS is reused by the next item
     }
     __syncthreads();  // D / cmd are rewritten by thread 0 for the next tick
   }
+}
+
+template <int WPE>
+__global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void qmx_tick_persistent(
+    PDoor* doors, PCtl* ctls, int wpd, uint32_t gen, uint32_t idle_ticks, int interleave) {
+  persistent_body<false>(doors, ctls, wpd, gen, idle_ticks, interleave);
+}
+
+// The multi-door grid of a class tag set (HipGrid, classes): the same loop around run_item<true>.
+// One workgroup per CU only — the class paths do not fit the 128 registers of two per CU.
+__global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2, 2))) void qmx_ctick_persistent(
+    PDoor* doors, PCtl* ctls, int wpd, uint32_t gen, uint32_t idle_ticks, int interleave) {
+  persistent_body<true>(doors, ctls, wpd, gen, idle_ticks, interleave);
 }
 
 // ------------------------------------------------------------------------------------
@@ -3513,12 +3531,19 @@ HipEngine::HipEngine(const std::vector<std::string>& tags, int device, int tile_
     persistent_ = false;
     poll_ = true;
   }
-  if (tag_classes(ts_) != nullptr) {
-    // class tags: the persistent grids run the literal tag sets' kernel only (its registers
-    // are spoken for); a class tag set ticks with a launch per tick, on tick lanes
-    if (grid_) throw std::invalid_argument("class thinking tags run on tick lanes (tick_mode lanes), not on the loop-tick grid");
-    persistent_ = false;
+  // a grid runs one kernel for all its doors: the literal tag sets' (qmx_tick_persistent) or
+  // the one that carries the class paths and reads KParams::cls (qmx_ctick_persistent, a grid
+  // made with `classes`) — the engine's tag set must be of the grid's kind
+  if (grid_ && (tag_classes(ts_) != nullptr) != grid_->classes()) {
+    if (!grid_->classes())
+      throw std::invalid_argument("class thinking tags run on tick lanes (tick_mode lanes) or on a loop-tick grid "
+                                  "made for them (HipGrid classes), not on a literal tag sets' grid");
+    throw std::invalid_argument("a class tag sets' loop-tick grid (HipGrid classes) takes engines with a class tag "
+                                "set only");
   }
+  // (tick lanes: a lane's own persistent grid is the literal kernel; a class tag set ticks
+  // with a launch per tick there)
+  if (tag_classes(ts_) != nullptr) persistent_ = false;
   HIP_CHECK(hipMalloc(&d_state_, sizeof(DevSlot) * (size_t)max_slots_));
   HIP_CHECK(hipMemset(d_state_, 0, sizeof(DevSlot) * (size_t)max_slots_));
   HIP_CHECK(hipMalloc(&d_content_, (size_t)content_cap_ * (size_t)max_slots_));
@@ -3706,7 +3731,7 @@ void HipEngine::set_persistent(bool on) {
       std::lock_guard<std::mutex> lg(L->mu);
       stop_persistent(*L);
     }
-  persistent_ = on && d_cls_ == nullptr;  // (a class tag set: a launch per tick)
+  persistent_ = on && d_cls_ == nullptr;  // (a class tag set on tick lanes: a launch per tick)
 }
 
 void HipEngine::debug_poison_results(int ahead) {
@@ -4743,8 +4768,12 @@ std::unordered_map<std::string, double> HipEngine::kernel_stats() {
 }
 
 // ---- the multi-door grid (loop ticks) ----------------------------------------------------
-HipGrid::HipGrid(int device, int doors, int wg_per_door, int idle_ms)
-    : device_(device), n_(std::max(1, doors)), wpd_(std::max(1, wg_per_door)), idle_ms_(std::max(5, idle_ms)) {
+HipGrid::HipGrid(int device, int doors, int wg_per_door, int idle_ms, bool classes)
+    : classes_(classes),
+      device_(device),
+      n_(std::max(1, doors)),
+      wpd_(std::max(1, wg_per_door)),
+      idle_ms_(std::max(5, idle_ms)) {
   // every workgroup of a persistent grid must be resident at once (a relay that is not never
   // relays its door's ticks), and the tick kernels run one workgroup per CU (LDS, VGPRs):
   // keep the grid within half the device's CUs — room for a second process's grid during a
@@ -4757,7 +4786,8 @@ HipGrid::HipGrid(int device, int doors, int wg_per_door, int idle_ms)
     const int sharers = sh ? std::max(1, atoi(sh)) : 1;
     // QMX_GRID_OCC=2: the register-capped kernel, two workgroups per CU — the budget is half
     // the device's workgroup slots, not half its CUs
-    if (const char* oc = env_get("QMX_GRID_OCC")) occ_ = atoi(oc) == 2 ? 2 : 1;
+    // (a class grid has no two-per-CU kernel: one workgroup per CU, its budget counted so)
+    if (const char* oc = env_get("QMX_GRID_OCC")) occ_ = !classes_ && atoi(oc) == 2 ? 2 : 1;
     const int cus = std::max(1, pr.multiProcessorCount), budget = cus * occ_ / 2 / sharers;
     if (n_ * wpd_ > budget) wpd_ = std::max(1, budget / n_);
     if (n_ * wpd_ > budget) throw std::runtime_error("grid: " + std::to_string(n_) + " doors do not fit " +
@@ -4809,7 +4839,10 @@ void HipGrid::launch_locked() {
   HIP_CHECK(hipSetDevice(device_));
   for (int d = 0; d < n_; ++d) h_doors_[d].base = __atomic_load_n(&h_doors_[d].relayed, __ATOMIC_ACQUIRE);
   const uint32_t idle_ticks = 2000u * 100000u;  // 2 s at 100 MHz: only a host that stopped beating
-  if (occ_ == 2)
+  if (classes_)  // (first launch, relaunch after an idle stop and revival alike)
+    hipLaunchKernelGGL(qmx_ctick_persistent, dim3(n_ * wpd_), dim3(BS), 0, stream_, h_doors_, d_ctls_, wpd_, ++gen_,
+                       idle_ticks, interleave_ ? 1 : 0);
+  else if (occ_ == 2)
     hipLaunchKernelGGL(qmx_tick_persistent<4>, dim3(n_ * wpd_), dim3(BS), 0, stream_, h_doors_, d_ctls_, wpd_, ++gen_,
                        idle_ticks, interleave_ ? 1 : 0);
   else
@@ -4940,6 +4973,7 @@ std::unordered_map<std::string, double> HipGrid::stats() {
           {"grid_revivals", (double)revivals_.load()}, {"grid_doors", (double)n_},
           {"grid_clock_rtt_us", clk_rtt_us_.load(std::memory_order_relaxed)}, {"grid_xcd_local", interleave_ ? 1.0 : 0.0},
           {"grid_wg_per_door", (double)wpd_}, {"grid_wg_per_cu", (double)occ_},
+          {"grid_classes", classes_ ? 1.0 : 0.0},  // 1: the class tag sets' kernel (qmx_ctick_persistent)
           // (written under the exclusive lock; a torn read of a double is harmless here)
           {"grid_launch_us_max", launch_us_max_}, {"grid_launch_calibrate_us_max", launch_cal_us_max_},
           {"grid_launch_us_sum", launch_us_sum_}, {"grid_stop_us_max", stop_us_max_}};

@@ -500,6 +500,7 @@ struct ResultBatch {
 // /metrics and logged.
 // --------------------------------------------------------------------------------------
 std::atomic<uint64_t> c_verify_checked{0}, c_verify_mismatch{0};
+std::atomic<uint64_t> c_class_grid_launches{0}, c_class_grid_ticks{0};  // server_counters()
 
 class Verifier {
  public:
@@ -1197,6 +1198,8 @@ class Loop {
         if (job_live_[k] && aeng_->job_ready(job_[k])) finish_job(k);
       if (jobs_live_) std::this_thread::sleep_for(std::chrono::microseconds(50));
     }
+    // server_counters(): the ticks this loop's doors ran on a class grid (the engine's own count)
+    if (heng_ && grid_ && grid_->classes()) c_class_grid_ticks += (uint64_t)heng_->kernel_stats()["grid_ticks"];
   }
   // deferred heads whose deadline passed are queued for this iteration's flush; entries whose
   // client was queued by later output (or closed) are dropped
@@ -3377,6 +3380,10 @@ class Loop {
     put("qmx_upstream_connections_total", (double)c_up_conns.load());
     put("qmx_client_connections_total", (double)c_clients.load());
     put("qmx_ticks_total", (double)c_ticks.load());
+    // which kernel the loop-tick grid runs: 1 the class tag sets' (qmx_ctick_persistent), 0 the
+    // literal one; no grid (tick lanes, CPU engine): the line is absent.  Launches and ticks:
+    // qmx_kernel_grid_launches / qmx_kernel_grid_ticks
+    if (grid_) put("qmx_grid_classes", grid_->classes() ? 1.0 : 0.0);
     put("qmx_output_coalesced_total", (double)c_coalesced.load());
     put("qmx_output_hold_seconds_sum", (double)c_hold_ns.load() * 1e-9);  // latency the holds added
     put("qmx_output_hold_seconds_count", (double)c_holds.load());
@@ -3711,9 +3718,11 @@ int run_server(const ServerCfg& cfg0) {
   // (rehearsals) split the grid budget: HipGrid sizes itself from QMX_GPU_SHARERS, and a grid
   // that does not fit falls back to lanes below.
   (void)spread;
-  // (a class tag set, runtime.native_regex_tags: tick lanes — the grid runs the literal kernel)
+  // A class tag set (runtime.native_regex_tags) takes loop ticks like a literal one: its grid
+  // is made with the flag and launches the kernel that carries the class paths
+  // (qmx_ctick_persistent); the loops' engines carry the same tag set, so they pair with it.
   const bool cls_tags = cfg.tag_classes && tag_classes(make_tagset(cfg.tags, true)) != nullptr;
-  const bool loop_ticks = hip && cfg.tick_mode != "lanes" && cfg.shared_engine != 1 && !cls_tags;
+  const bool loop_ticks = hip && cfg.tick_mode != "lanes" && cfg.shared_engine != 1;
   const bool shared = !loop_ticks && (cfg.shared_engine < 0 ? hip : cfg.shared_engine > 0);
   if (shared) hub.reset(new GpuHub(cfg, (int)loops.size()));
   if (loop_ticks) {
@@ -3722,11 +3731,12 @@ int run_server(const ServerCfg& cfg0) {
     const char* fl = env_get("QMX_LOOP_INFLIGHT");
     const int per_loop = fl ? std::min(std::max(atoi(fl), 1), 2) : 2;  // doors per loop (as Loop::loop_doors_)
     try {
-      // (QMX_GRID_OCC=2: two workgroups per CU — twice the workgroups per door by default)
+      // (QMX_GRID_OCC=2: two workgroups per CU — twice the workgroups per door by default; the
+      // class grid has the one-per-CU kernel only)
       const char* oc = env_get("QMX_GRID_OCC");
-      const int wpd0 = oc && atoi(oc) == 2 ? 16 : 8;
+      const int wpd0 = !cls_tags && oc && atoi(oc) == 2 ? 16 : 8;
       grid.reset(new HipGrid(cfg.device, (int)loops.size() * per_loop, w ? std::max(1, atoi(w)) : wpd0,
-                             im ? atoi(im) : 50));
+                             im ? atoi(im) : 50, cls_tags));
     } catch (const std::exception& e) {  // e.g. more io loops than a partitioned GPU has CUs
       fprintf(stderr, "qmx: loop ticks unavailable (%s) — tick lanes instead\n", e.what());
       hub.reset(new GpuHub(cfg, (int)loops.size()));
@@ -3838,6 +3848,7 @@ int run_server(const ServerCfg& cfg0) {
   }
   hub.reset();  // tick thread joined before the loops (its result sinks) go away
   if (grid) grid->stop();  // before the loops' engines free what the grid may touch
+  if (grid && grid->classes()) c_class_grid_launches += (uint64_t)grid->stats()["grid_launches"];
   loops.clear();
   grid.reset();
   if (tls) SSL_CTX_free(tls);
@@ -3850,7 +3861,11 @@ std::unordered_map<std::string, double> server_counters() {
   return {{"requests", (double)c_requests.load()}, {"errors", (double)c_errors.load()},
           {"ticks", (double)c_ticks.load()}, {"upstream_failures", (double)c_up_fail.load()},
           {"verify_checked", (double)c_verify_checked.load()},
-          {"verify_mismatches", (double)c_verify_mismatch.load()}};
+          {"verify_mismatches", (double)c_verify_mismatch.load()},
+          // loop ticks of a class tag set, summed over the servers that have shut down: launches
+          // of the class grid kernel and the ticks its doors ran
+          {"class_grid_launches", (double)c_class_grid_launches.load()},
+          {"class_grid_ticks", (double)c_class_grid_ticks.load()}};
 }
 
 }  // namespace qmx

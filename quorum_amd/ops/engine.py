@@ -181,7 +181,9 @@ def make_engine(kind: str, tags: Sequence[str], device: Optional[int] = None, **
     """Build (and cache per process) an engine for a tag set.
 
     ``kind``: "auto" | "hip" | "cpu" | "python".  "hip" raises loudly when the HIP
-    extension or a GPU is missing (no silent fallback on a GPU box).
+    extension or a GPU is missing (no silent fallback on a GPU box).  ``opts`` go to the
+    native engine as they are; a ``grid`` among them must be of the tag set's kind
+    (``native.make_grid(tags, ..., classes=classes)``: the class grid for a class tag set).
     """
     tags = list(tags)
     classes = bool(opts.pop("classes", False))

@@ -66,6 +66,16 @@ def strip_fn(tags: Sequence[str], classes: bool = False) -> Callable[[str, bool]
     return _strip
 
 
+def make_grid(tags: Sequence[str], device: int, doors: int, wg_per_door: int = 8, idle_ms: int = 50,
+              classes: bool = False):
+    """A multi-door loop-tick grid (``HipGrid``) of the kind this tag set's engines need: the
+    class kernel for a class tag set (``classes`` on and a '.' or bracket class in a tag), the
+    literal kernel otherwise.  Every ``NativeEngine`` given the grid must use the same tags."""
+    ext = require()
+    cls = bool(classes) and ext.tagset_has_classes(list(tags), True)
+    return ext.HipGrid(device, doors, wg_per_door, idle_ms, classes=cls)
+
+
 class NativeEngine:
     """Python face of the C++ engines (``cpu`` = host library, ``hip`` = GPU tick kernels)."""
 
@@ -88,7 +98,8 @@ class NativeEngine:
                 raise RuntimeError("engine 'hip' requested but no GPU is visible")
             if device is None:
                 device = int(os.environ.get("LOCAL_RANK", "0")) % max(ext.device_count(), 1)
-            # grid: a HipGrid (loop ticks) — this engine posts its ticks into door `door` of it
+            # grid: a HipGrid (loop ticks) — this engine posts its ticks into door `door` of it.
+            # A class tag set needs a grid made with classes=True (make_grid picks the kind)
             self._e = ext.HipEngine(low, device, tile_bytes, max_slots, content_cap, lanes, grid, door, ndoors,
                                      classes=self.classes)
             self.offload = True

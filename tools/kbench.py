@@ -64,8 +64,9 @@ def main():
                     help="stream the body N events per tick (steady-state serving shape); 0 = whole body in one tick")
     ap.add_argument("--tags", default="think,reason,reasoning,thought", help="comma-separated thinking tags")
     ap.add_argument("--classes", action="store_true",
-                    help="class tags ('.', '[...]': runtime.native_regex_tags), e.g. --tags think,th.nk; one-shot "
-                         "launches only (a class tag set does not run on the persistent grid)")
+                    help="class tags ('.', '[...]': runtime.native_regex_tags), e.g. --tags think,th.nk: one-shot "
+                         "launches (qmx_ctick_kernel), or with --grid N a class grid (HipGrid classes=True, "
+                         "qmx_ctick_persistent)")
     args = ap.parse_args()
     from quorum_amd.ops.native import NativeEngine
 
@@ -76,7 +77,9 @@ def main():
     if args.grid > 0:
         from quorum_amd.ops import native
 
-        grid = native.require().HipGrid(0, args.grid, 8)
+        ext = native.require()
+        # a class tag set runs on a grid of its own kind (the class kernel)
+        grid = ext.HipGrid(0, args.grid, 8, classes=args.classes and ext.tagset_has_classes(tags, True))
     combos = {"ft": (True, True), "f": (True, False), "t": (False, True)}
     for filt, emit in [combos[c] for c in args.combos.split(",")]:
         for n in [int(x) for x in args.slots.split(",")]:
@@ -123,6 +126,7 @@ def main():
             if grid is not None:
                 rec["grid_ticks"] = st.get("grid_ticks")
                 rec["grid_launches"] = st.get("grid_launches")
+                rec["grid_classes"] = st.get("grid_classes")  # 1: the class kernel ran the ticks
             results.append(rec)
             print(json.dumps(rec), flush=True)
     if grid is not None:  # the grid's one dispatch ends here: its counters cover every tick above
