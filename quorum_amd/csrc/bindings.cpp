@@ -25,7 +25,8 @@ namespace {
 struct PyStreamFilter {
   TagSet ts;
   FilterState fs;
-  PyStreamFilter(const std::vector<std::string>& tags, bool classes) : ts(make_tagset(tags, classes)) {}
+  PyStreamFilter(const std::vector<std::string>& tags, bool classes, bool unicode)
+      : ts(make_tagset(tags, classes, unicode)) {}
   py::bytes feed(const std::string& s) {
     std::string out;
     filter_feed(ts, fs, (const uint8_t*)s.data(), s.size(), out);
@@ -39,7 +40,7 @@ struct PyStreamFilter {
 
 struct PyStripper {
   TagSet ts;
-  PyStripper(const std::vector<std::string>& tags, bool classes) : ts(make_tagset(tags, classes)) {}
+  PyStripper(const std::vector<std::string>& tags, bool classes, bool unicode) : ts(make_tagset(tags, classes, unicode)) {}
   py::bytes strip(const std::string& s) { return py::bytes(strip_final(ts, (const uint8_t*)s.data(), s.size())); }
 };
 
@@ -138,6 +139,7 @@ ServerCfg server_cfg_from(const py::dict& d) {
   gb("skip_final", c.skip_final); gb("suppress", c.suppress);
   if (d.contains("tags")) c.tags = py::cast<std::vector<std::string>>(d["tags"]);
   gb("tag_classes", c.tag_classes);
+  gb("tag_unicode", c.tag_unicode);
   gs("aggregator_name", c.aggregator_name); gs("prompt_template", c.prompt_template);
   gs("intermediate_separator", c.intermediate_separator); gs("query_format", c.query_format);
   gs("source_label_format", c.source_label_format); gb("include_original_query", c.include_original_query);
@@ -475,26 +477,49 @@ PYBIND11_MODULE(_qmx, m) {
     return py::bytes(out);
   });
   py::class_<PyStreamFilter>(m, "StreamFilter")
-      .def(py::init<const std::vector<std::string>&, bool>(), py::arg("tags"), py::arg("classes") = false)
+      .def(py::init<const std::vector<std::string>&, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
+           py::arg("unicode") = false)
       .def("feed", &PyStreamFilter::feed)
       .def("flush", &PyStreamFilter::flush);
   py::class_<PyStripper>(m, "Stripper")
-      .def(py::init<const std::vector<std::string>&, bool>(), py::arg("tags"), py::arg("classes") = false)
+      .def(py::init<const std::vector<std::string>&, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
+           py::arg("unicode") = false)
       .def("strip", &PyStripper::strip);
   // is this tag list inside what make_tagset runs natively (the one definition of the subset)?
-  m.def("tagset_ok", [](const std::vector<std::string>& tags, bool classes) {
+  m.def("tagset_ok", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
     try {
-      make_tagset(tags, classes);
+      make_tagset(tags, classes, unicode);
       return true;
     } catch (const std::invalid_argument&) {
       return false;
     }
-  }, py::arg("tags"), py::arg("classes") = false);
+  }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
+  // why make_tagset refuses this tag list ("" when it does not): the limit's own message
+  m.def("tagset_error", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
+    try {
+      make_tagset(tags, classes, unicode);
+      return std::string();
+    } catch (const std::invalid_argument& e) {
+      return std::string(e.what());
+    }
+  }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
+  // distinct tags of the set make_tagset builds ("É" and "é" are one)
+  m.def("tagset_size", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
+    return make_tagset(tags, classes, unicode).n;
+  }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
+  // the case rule of one non-ASCII tag character (qmx_unicode_fold.h): (kind, partner) with
+  // kind 0 uncased, 1 a simple case pair, 2 refused; partner: the pair's other member, else cp
+  m.def("unicode_tag_char", [](uint32_t cp) {
+    uint32_t low = cp;
+    const int kind = unicode_tag_char(cp, &low);
+    return py::make_tuple(kind, kind == 1 ? unicode_tag_partner(cp) : cp);
+  });
   // does this tag list make a class tag set (a '.', a bracket class)?  The test HipEngine uses
   // to pair an engine with a grid: a class tag set needs HipGrid(classes=True)
-  m.def("tagset_has_classes", [](const std::vector<std::string>& tags, bool classes) {
-    return tag_classes(make_tagset(tags, classes)) != nullptr;
-  }, py::arg("tags"), py::arg("classes") = true);
+  // (a pair tag set — `unicode` and a cased non-ASCII character in a tag — is of that kind too)
+  m.def("tagset_has_classes", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
+    return tag_classes(make_tagset(tags, classes, unicode)) != nullptr;
+  }, py::arg("tags"), py::arg("classes") = true, py::arg("unicode") = false);
   // candidates '<' of `text` the GPU kernels would hand to the host path (qmx_text.h
   // class_candidate, the shared suspect rule), with the streaming or the strip tables
   m.def("class_suspects", [](const std::vector<std::string>& tags, const std::string& text, bool strip) {
@@ -511,11 +536,11 @@ PYBIND11_MODULE(_qmx, m) {
   }, py::arg("tags"), py::arg("text"), py::arg("strip") = false);
   env_refresh();
   py::class_<CpuEngine> ce(m, "CpuEngine");
-  ce.def(py::init([](const std::vector<std::string>& tags, bool classes) {
+  ce.def(py::init([](const std::vector<std::string>& tags, bool classes, bool unicode) {
            env_refresh();
-           return new CpuEngine(tags, classes);
+           return new CpuEngine(tags, classes, unicode);
          }),
-         py::arg("tags"), py::arg("classes") = false);
+         py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
   bind_engine(ce);
   // the multi-door grid of loop ticks (tests drive several door engines from Python threads)
   py::class_<HipGrid>(m, "HipGrid")
@@ -560,13 +585,14 @@ PYBIND11_MODULE(_qmx, m) {
         py::call_guard<py::gil_scoped_release>());
   py::class_<HipEngine> he(m, "HipEngine");
   he.def(py::init([](const std::vector<std::string>& tags, int device, int tile, int max_slots, int content_cap,
-                      int lanes, HipGrid* grid, int door, int ndoors, bool classes) {
+                      int lanes, HipGrid* grid, int door, int ndoors, bool classes, bool unicode) {
            env_refresh();
-           return new HipEngine(tags, device, tile, max_slots, content_cap, lanes, grid, door, ndoors, classes);
+           return new HipEngine(tags, device, tile, max_slots, content_cap, lanes, grid, door, ndoors, classes,
+                                unicode);
          }),
          py::arg("tags"), py::arg("device"), py::arg("tile_bytes") = 16384, py::arg("max_slots") = 8192,
          py::arg("content_cap") = 1 << 20, py::arg("lanes") = 1, py::arg("grid") = nullptr, py::arg("door") = -1,
-         py::arg("ndoors") = 1, py::arg("classes") = false, py::keep_alive<1, 8>());
+         py::arg("ndoors") = 1, py::arg("classes") = false, py::arg("unicode") = false, py::keep_alive<1, 8>());
   bind_engine(he);
   he.def("kernel_stats", &HipEngine::kernel_stats);
   he.def("debug_poison_results", &HipEngine::debug_poison_results, py::arg("ahead") = 1);

@@ -1,6 +1,7 @@
 // qmx_engine.cpp — host engine core + the sequential (oracle-equivalent) CPU algorithms.
 #include "qmx_env.h"
 #include "qmx_engine.h"
+#include "qmx_unicode_fold.h"
 
 #include <cstdlib>
 #include <ctime>
@@ -120,25 +121,94 @@ int cls_n = 0;
 
 }  // namespace
 
-TagSet make_tagset(const std::vector<std::string>& tags, bool classes) {
+// The case rule of a non-ASCII tag character (qmx_unicode_fold.h, generated from the rule in
+// tools/gen_unicode_fold.py).  0: uncased, 1: a pair (*lower: its lower member, which may be
+// cp itself), 2: refused.
+int unicode_tag_char(uint32_t cp, uint32_t* lower) {
+  *lower = cp;
+  if (cp < 0x80) return 0;
+  for (int k = 0; k < kFoldRefusedCount; ++k)
+    if (cp >= kFoldRefused[k][0] && cp <= kFoldRefused[k][1]) return 2;
+  for (int k = 0; k < kFoldPairCount; ++k) {
+    if (kFoldPairs[k][0] == cp) {
+      *lower = kFoldPairs[k][1];
+      return 1;
+    }
+    if (kFoldPairs[k][1] == cp) return 1;
+  }
+  return 0;
+}
+
+uint32_t unicode_tag_partner(uint32_t cp) {
+  for (int k = 0; k < kFoldPairCount; ++k) {
+    if (kFoldPairs[k][0] == cp) return kFoldPairs[k][1];
+    if (kFoldPairs[k][1] == cp) return kFoldPairs[k][0];
+  }
+  return cp;
+}
+
+TagSet make_tagset(const std::vector<std::string>& tags, bool classes, bool unicode) {
   TagSet ts;
   std::memset(&ts, 0, sizeof(ts));
   TagClasses tc;
   std::memset(&tc, 0, sizeof(tc));
-  bool any_cls = false;
+  bool any_cls = false, any_wide = false;
   std::vector<std::string> seen;
+  auto pack = [](uint32_t cp, int* len) {  // UTF-8 bytes, byte k at bit 8k
+    uint8_t b[4];
+    *len = put_wtf8(cp, b);
+    uint32_t v = 0;
+    for (int k = 0; k < *len; ++k) v |= (uint32_t)b[k] << (8 * k);
+    return v;
+  };
   for (const auto& t0 : tags) {
     std::string t;
-    for (char c : t0) t.push_back((char)lower_ascii((uint8_t)c));
+    bool wide = false;
+    for (char c : t0) wide = wide || (uint8_t)c >= 0x80;
+    if (wide && unicode) {
+      // a non-ASCII tag: its characters are uncased or one of a simple case pair, lowercased
+      // here through the pair table ("É" and "é" are one tag)
+      const uint8_t* b = (const uint8_t*)t0.data();
+      const int n = (int)t0.size();
+      if (!utf8_valid(b, 0, n)) throw std::invalid_argument("tag is not UTF-8: " + t0);
+      for (int p = 0; p < n;) {
+        uint32_t cp, low;
+        p += wtf8_decode(b, p, n, &cp);
+        if (cp < 0x80) {
+          t.push_back((char)lower_ascii((uint8_t)cp));
+          continue;
+        }
+        const int kind = unicode_tag_char(cp, &low);
+        if (kind == 2)
+          throw std::invalid_argument("tag holds a character without a simple case pair (runs with --impl python): " + t0);
+        uint8_t o[4];
+        t.append((const char*)o, (size_t)put_wtf8(low, o));
+        if (kind == 1) {
+          int ln;
+          const uint32_t lo = pack(low, &ln), up = pack(unicode_tag_partner(low), &ln);
+          int f = 0;
+          while (f < tc.nfold && tc.fold_lo[f] != lo) ++f;
+          if (f == tc.nfold) {
+            if (tc.nfold >= kMaxFold) throw std::invalid_argument("too many case-pair characters in the thinking tags (at most 32)");
+            tc.fold_lo[f] = lo;
+            tc.fold_up[f] = up;
+            tc.fold_len[f] = (uint8_t)ln;
+            ++tc.nfold;
+          }
+        }
+      }
+    } else {
+      for (char c : t0) t.push_back((char)lower_ascii((uint8_t)c));
+    }
     if (std::find(seen.begin(), seen.end(), t) != seen.end()) continue;
     // regex metacharacters change what quorum's alternation matches (oai_proxy.py:137,
     // 271-274); '<', '>' and '/' in a tag let one tag's pattern start inside another's, so
-    // the token model (at most one pattern per '<') would not hold; non-ASCII would need
-    // Unicode case folding.  Everything else is literal, exactly as in the regex.
+    // the token model (at most one pattern per '<') would not hold; non-ASCII needs the case
+    // rule above (`unicode`).  Everything else is literal, exactly as in the regex.
     bool literal = true;
     for (char ch : t) {
       const uint8_t c = (uint8_t)ch;
-      const bool ok = c >= 0x20 && c < 0x7f && !std::strchr(".^$*+?{}[]\\|()<>/", (int)c);
+      const bool ok = (c >= 0x20 && c < 0x7f && !std::strchr(".^$*+?{}[]\\|()<>/", (int)c)) || (unicode && c >= 0x80);
       if (!ok) literal = false;
     }
     if (t.empty() || (int)t.size() > kMaxTagLen) {
@@ -156,6 +226,7 @@ TagSet make_tagset(const std::vector<std::string>& tags, bool classes) {
     }
     if (ts.n >= kMaxTags) throw std::invalid_argument("too many thinking tags");
     seen.push_back(t);
+    any_wide = any_wide || (literal && wide);
     tc.srclen[ts.n] = (int)t.size();
     std::memcpy(tc.src[ts.n], t.data(), t.size());
     if (literal) {
@@ -184,7 +255,13 @@ TagSet make_tagset(const std::vector<std::string>& tags, bool classes) {
     ++ts.n;
   }
   if (ts.n == 0) throw std::invalid_argument("empty tag set");
-  if (any_cls) {
+  // a class position is kept as byte 0x80 + k in TagSet::name, where a non-ASCII tag keeps
+  // its UTF-8 bytes
+  if (any_cls && any_wide)
+    throw std::invalid_argument("class tags and non-ASCII tags do not mix in one tag set (runs with --impl python)");
+  if (tc.nfold > 0)
+    for (int pat = 0; pat < 2 * ts.n; ++pat) tc.span = std::max(tc.span, pattern_len(ts, pat));
+  if (any_cls || tc.nfold > 0) {
     // interned: TagSet is copied by value everywhere (kernel parameters included) and keeps
     // only the id; the tables live for the process, one entry per distinct class tag set
     std::lock_guard<std::mutex> g(cls_mu);
@@ -221,13 +298,15 @@ void filter_feed(const TagSet& ts, FilterState& fs, const uint8_t* text, size_t 
   int i = 0;
   fs.tail_len = 0;
   const TagClasses* tc = tag_classes(ts);
-  const bool cls = tc != nullptr;
+  const bool pair = tc != nullptr && tc->nfold > 0;  // literal tags, the text folded on read
+  const bool cls = tc != nullptr && !pair;
   while (true) {
     // next token at or after i (depth 0: opens only are tokens)
     int p = i, tok = 0, L = 0;
     for (; p < N; ++p) {
       if (x[p] != '<') continue;
-      tok = cls ? class_match_at(x, N, p, ts, *tc, false, &L) : match_at(x, N, p, ts, &L);
+      tok = cls ? class_match_at(x, N, p, ts, *tc, false, &L)
+                : pair ? fold_match_at(x, N, p, ts, *tc, &L) : match_at(x, N, p, ts, &L);
       if (tok > 0 || (tok < 0 && fs.depth > 0)) break;
       tok = 0;
     }
@@ -253,7 +332,9 @@ void filter_feed(const TagSet& ts, FilterState& fs, const uint8_t* text, size_t 
       hold = q < N;
     } else {
       while (q >= i && x[q] != '<') --q;
-      hold = q >= i && (cls ? source_prefix(x, q, N, ts, *tc) : pattern_prefix(x, q, N, ts, fs.depth == 0));
+      hold = q >= i && (cls ? source_prefix(x, q, N, ts, *tc)
+                            : pair ? fold_pattern_prefix(x, q, N, ts, *tc, fs.depth == 0)
+                                   : pattern_prefix(x, q, N, ts, fs.depth == 0));
     }
     int cut = hold ? q : N;
     if (fs.depth == 0) out.append((const char*)x + i, cut - i);
@@ -313,13 +394,16 @@ static std::string strip_final_classes(const TagSet& ts, const TagClasses& tc, c
 }
 
 std::string strip_final(const TagSet& ts, const uint8_t* x, size_t n) {
-  if (const TagClasses* tc = tag_classes(ts)) return strip_final_classes(ts, *tc, x, (int)n);
+  const TagClasses* tc = tag_classes(ts);
+  if (tc != nullptr && tc->nfold == 0) return strip_final_classes(ts, *tc, x, (int)n);
+  // (a pair tag set: the tokens of the folded text — the backreference folds both sides, so a
+  // close of the same tag in any case is the open's close, as for ASCII letters)
   struct Tok { int pos, len, id; };
   std::vector<Tok> toks;
   for (int p = 0; p < (int)n; ++p) {
     if (x[p] != '<') continue;
     int L = 0;
-    int id = match_at(x, (int)n, p, ts, &L);
+    int id = tc != nullptr ? fold_match_at(x, (int)n, p, ts, *tc, &L) : match_at(x, (int)n, p, ts, &L);
     if (id != 0) toks.push_back({p, L, id});
   }
   std::vector<int> next_close(toks.size(), -1);
@@ -535,7 +619,8 @@ static double mono_s() {
   return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
-HostEngine::HostEngine(const std::vector<std::string>& tags, bool classes) : ts_(make_tagset(tags, classes)) {
+HostEngine::HostEngine(const std::vector<std::string>& tags, bool classes, bool unicode)
+    : ts_(make_tagset(tags, classes, unicode)) {
   if (const char* pe = env_get("QMX_PIPELINE")) pipeline_ = atoi(pe) != 0;
 }
 
@@ -817,7 +902,8 @@ struct AsyncCpuEngine::Done {
   std::atomic<bool> ready{false};
 };
 
-AsyncCpuEngine::AsyncCpuEngine(const std::vector<std::string>& tags, bool classes) : CpuEngine(tags, classes) {
+AsyncCpuEngine::AsyncCpuEngine(const std::vector<std::string>& tags, bool classes, bool unicode)
+    : CpuEngine(tags, classes, unicode) {
   th_ = std::thread([this] { run(); });
 }
 

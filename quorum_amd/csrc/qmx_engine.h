@@ -29,7 +29,12 @@ namespace qmx {
 enum ResultFlags : int { RF_DONE = 1, RF_ABORTED = 2, RF_ESCALATED = 4 };
 
 // classes: also accept class tags ("." / "[...]" / escaped punctuation; qmx_text.h TagClasses)
-TagSet make_tagset(const std::vector<std::string>& tags, bool classes = false);
+// unicode: also accept non-ASCII tags whose characters are uncased or one of a simple case
+// pair (qmx_unicode_fold.h); a tag set with a pair character is a pair tag set (TagClasses::nfold)
+TagSet make_tagset(const std::vector<std::string>& tags, bool classes = false, bool unicode = false);
+// the case rule of a non-ASCII tag character: 0 uncased, 1 a pair (*lower: its lower member), 2 refused
+int unicode_tag_char(uint32_t cp, uint32_t* lower);
+uint32_t unicode_tag_partner(uint32_t cp);  // the other member of cp's pair (cp: none)
 // the class tables and source text of a class tag set (null for a literal one)
 const TagClasses* tag_classes(const TagSet& ts);
 
@@ -161,7 +166,7 @@ class SlotTable {
 
 class HostEngine {
  public:
-  explicit HostEngine(const std::vector<std::string>& tags, bool classes = false);
+  explicit HostEngine(const std::vector<std::string>& tags, bool classes = false, bool unicode = false);
   virtual ~HostEngine() = default;
 
   // returns the slot; *gen (optional) receives the slot's open generation (SlotResult::gen)
@@ -286,7 +291,8 @@ class HostEngine {
 
 class CpuEngine : public HostEngine {
  public:
-  explicit CpuEngine(const std::vector<std::string>& tags, bool classes = false) : HostEngine(tags, classes) {}
+  explicit CpuEngine(const std::vector<std::string>& tags, bool classes = false, bool unicode = false)
+      : HostEngine(tags, classes, unicode) {}
   // pipelined lanes on the CPU: the whole tick runs in job_complete (exercises GpuHub's
   // pipelined loop without a GPU)
   bool pipelined() const override { return pipeline_; }
@@ -306,7 +312,7 @@ class CpuEngine : public HostEngine {
 // CPU and TSan suites, where no GPU is.
 class AsyncCpuEngine : public CpuEngine {
  public:
-  explicit AsyncCpuEngine(const std::vector<std::string>& tags, bool classes = false);
+  explicit AsyncCpuEngine(const std::vector<std::string>& tags, bool classes = false, bool unicode = false);
   ~AsyncCpuEngine() override;
   bool async_jobs() const override { return true; }
   void job_post(Job& j) override;

@@ -313,7 +313,8 @@ class HipEngine : public HostEngine {
  public:
   // grid: loop-tick mode — one lane whose ticks go to door `door` of a shared multi-door grid
   HipEngine(const std::vector<std::string>& tags, int device, int tile_bytes, int max_slots, int content_cap,
-            int lanes = 1, HipGrid* grid = nullptr, int door = -1, int ndoors = 1, bool classes = false);
+            int lanes = 1, HipGrid* grid = nullptr, int door = -1, int ndoors = 1, bool classes = false,
+            bool unicode = false);
   ~HipEngine() override;
   // loop-tick mode (the io loop drives its own ticks): has the posted job's every result been
   // published?  Never blocks.  expect_us: the job's expected remaining time (poll timing).

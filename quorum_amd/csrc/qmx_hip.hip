@@ -463,7 +463,31 @@ __device__ inline bool pattern_prefix_w(const uint8_t* Z, int q, int e, const KP
 // candidate's token — `lit` (the fast matcher's), or the class tag's when it comes first in the
 // tag list — or kClsSuspect.
 constexpr int kClsSuspect = 0x100;
+// Pair tag sets (TagClasses::nfold > 0: literal tags with a cased non-ASCII character) are of
+// the class kind for one reason: the text is folded as it is read, the upper member of a pair
+// standing for its lower member.  The fast matchers compare bytes, so they find every tag
+// written in lower case; a candidate they left is walked here with the fold — only when a byte
+// >= 0x80 lies within the longest pattern's reach of it: an ASCII window has nothing to fold.
+// The class walks never run for such a set (they read a name byte >= 0x80 as a class marker).
+// (Out of line, and results in registers only: the class kernels keep their register budget —
+// tests/test_isa_class_grid.py — and these walks run for the few candidates that need them.)
+__device__ __noinline__ int fold_match_dev(const uint8_t* x, int n, int p, const TagSet* ts, const TagClasses* tc) {
+  int len = 0;
+  return fold_match_at(x, n, p, *ts, *tc, &len);  // (the token's length: pattern_len of its id)
+}
+__device__ __noinline__ int fold_prefix_dev(const uint8_t* x, int q, int e, const TagSet* ts, const TagClasses* tc,
+                                            int opens_only) {
+  return fold_pattern_prefix(x, q, e, *ts, *tc, opens_only != 0) ? 1 : 0;
+}
+__device__ inline int fold_token(const uint8_t* Z, int Zn, int p, const KParams& P) {
+  uint64_t hb = 0;
+  const int span = P.cls->span;
+  for (int o = 0; o < span && p + o < Zn; o += 8) hb |= lds_window8(Z, p + o, Zn);  // (reads end before Zn + 16)
+  if ((hb & 0x8080808080808080ull) == 0) return 0;
+  return fold_match_dev(Z, Zn, p, &P.ts, P.cls);
+}
 __device__ __forceinline__ int class_token(const uint8_t* Z, int Zn, int p, const KParams& P, int lit) {
+  if (P.cls->nfold > 0) return lit != 0 ? lit : fold_token(Z, Zn, p, P);
   int tok = 0, len = 0;
   const int r = class_candidate(Z, Zn, p, P.ts, *P.cls, false, &tok, &len);
   if (r == CC_SUSPECT) return kClsSuspect;
@@ -477,6 +501,7 @@ __device__ __forceinline__ int class_token(const uint8_t* Z, int Zn, int p, cons
 // Inside a block: a proper class-aware prefix of any pattern.  Bit 0: hold.
 __device__ __forceinline__ int class_hold(const uint8_t* Z, int q, int e, const KParams& P, int dq, int tk) {
   if (e - q > kMaxTail) return 0;
+  if (P.cls->nfold > 0) return fold_prefix_dev(Z, q, e, &P.ts, P.cls, dq == 0);  // (a pair tag set)
   if (dq == 0) {
     const bool pre = source_prefix(Z, q, e, P.ts, *P.cls);
     return (pre ? 1 : 0) | (tk > 0 && !pre ? 2 : 0);
@@ -2558,6 +2583,11 @@ enum : int { FV_CUR = 0, FV_PEND, FV_SEGA, FV_NSEG, FV_NTOK, FV_S0, FV_S1, FV_NB
 // when the candidate is suspect (qmx_text.h class_candidate).
 __device__ __forceinline__ int fin_class_token(const uint8_t* __restrict__ src, int n, int p, const TagSet& ts,
                                                const TagClasses& tc, int* L) {
+  if (tc.nfold > 0) {  // a pair tag set: the folded text's token
+    const int id = fold_match_dev(src, n, p, &ts, &tc);
+    if (id != 0) *L = id > 0 ? ts.len[id - 1] + 2 : ts.len[-id - 1] + 3;
+    return id;
+  }
   int lit_len = 0, tok = 0, len = 0;
   const int lit = match_at(src, n, p, ts, &lit_len);
   const int r = class_candidate(src, n, p, ts, tc, true, &tok, &len);
@@ -2658,7 +2688,9 @@ __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n
             if constexpr (CLS) {  // the close's name against the open's captured bytes, a byte per lane
               wave_fence();  // (FV_PPOS: lane 0's store at the open, maybe a window ago)
               const int ppos = F.v[FV_PPOS], cpos = __shfl(pos, L, 64), nl = ts.len[pend - 1];
-              const bool ne = lane < nl && lower_ascii(src[ppos + 1 + lane]) != lower_ascii(src[cpos + 2 + lane]);
+              // (a pair tag set's tags are literal: open and close of one tag fold to the same bytes)
+              const bool ne = lane < nl && tc->nfold == 0 &&
+                              lower_ascii(src[ppos + 1 + lane]) != lower_ascii(src[cpos + 2 + lane]);
               if (__ballot(ne) != 0 && lane == 0) F.v[FV_CLS] = 1;
             }
             cur = __shfl(end, L, 64);
@@ -3492,8 +3524,8 @@ void HipEngine::collect_timing(TickLane& L) {
 }
 
 HipEngine::HipEngine(const std::vector<std::string>& tags, int device, int tile_bytes, int max_slots,
-                     int content_cap, int lanes, HipGrid* grid, int door, int ndoors, bool classes)
-    : HostEngine(tags, classes),
+                     int content_cap, int lanes, HipGrid* grid, int door, int ndoors, bool classes, bool unicode)
+    : HostEngine(tags, classes, unicode),
       device_(device),
       tile_(std::min(std::max(tile_bytes, 1024), TILE_MAX) & ~15),
       max_slots_(max_slots),
@@ -3566,7 +3598,7 @@ HipEngine::HipEngine(const std::vector<std::string>& tags, int device, int tile_
     for (int p = 0; p < base_params_.npat; ++p)
       for (int j = 0; j < pattern_len(ts_, p); ++j) {
         const uint8_t b = pattern_byte(ts_, p, j);
-        if (b >= 0x80 || base_params_.code[b] != 95) continue;  // (a class position is no byte)
+        if (b >= 0x80 || base_params_.code[b] != 95) continue;  // (a class position is no byte; a non-ASCII tag's UTF-8 bytes have no case)
         if (next > 94) throw std::invalid_argument("thinking tags use more than 94 distinct characters");
         base_params_.code[b] = (uint8_t)next;
         if (b >= 'a' && b <= 'z') base_params_.code[b - 32] = (uint8_t)next;

@@ -504,7 +504,7 @@ std::atomic<uint64_t> c_class_grid_launches{0}, c_class_grid_ticks{0};  // serve
 
 class Verifier {
  public:
-  Verifier(const std::vector<std::string>& tags, bool classes) : cpu_(tags, classes) {}
+  Verifier(const std::vector<std::string>& tags, bool classes, bool unicode) : cpu_(tags, classes, unicode) {}
   void open(int slot, uint32_t gen, int index, bool f, bool e) {
     std::lock_guard<std::mutex> g(mu_);
     Track t;
@@ -687,7 +687,7 @@ class GpuHub {
     lanes_ = std::max(1, std::min(cfg.tick_lanes, 8));
     if (cfg.engine == "hip") {
       HipEngine* he = new HipEngine(cfg.tags, cfg.device, cfg.tile, cfg.max_slots, cfg.content_cap, lanes_, nullptr, -1,
-                                     1, cfg.tag_classes);
+                                     1, cfg.tag_classes, cfg.tag_unicode);
       he->set_remote_hbm_direct(remote_hbm_direct(cfg));
       // (spread placement: an RCCL round writes a remote final text into the content arena
       // and its stream is synchronised before the text is applied; the finalize that reads it
@@ -695,8 +695,8 @@ class GpuHub {
       // persistent grids alike)
       eng_.reset(he);
     } else
-      eng_.reset(new CpuEngine(cfg.tags, cfg.tag_classes));  // shared CPU engine: exercises the hub routing on CPU
-    if (cfg.verify) ver_.reset(new Verifier(cfg.tags, cfg.tag_classes));
+      eng_.reset(new CpuEngine(cfg.tags, cfg.tag_classes, cfg.tag_unicode));  // shared CPU engine: exercises the hub routing on CPU
+    if (cfg.verify) ver_.reset(new Verifier(cfg.tags, cfg.tag_classes, cfg.tag_unicode));
   }
   ~GpuHub() {
     {
@@ -1260,7 +1260,7 @@ class Loop {
         prctl(PR_SET_TIMERSLACK, 1000UL, 0, 0, 0);  // 1 us: the tick polls sleep a few us
         const int per = std::max(128, cfg_.max_slots / std::max(1, cfg_.threads));
         heng_ = new HipEngine(cfg_.tags, cfg_.device, cfg_.tile, per, cfg_.content_cap, 1, grid_,
-                              idx_ * loop_doors_, loop_doors_, cfg_.tag_classes);
+                              idx_ * loop_doors_, loop_doors_, cfg_.tag_classes, cfg_.tag_unicode);
         heng_->set_remote_hbm_direct(remote_hbm_direct(cfg_));
         eng_.reset(heng_);
         aeng_ = heng_;
@@ -1268,12 +1268,12 @@ class Loop {
       } else if (cfg_.tick_mode == "loops") {
         // the loop-tick protocol on the CPU: jobs run on the engine's worker thread while the
         // loop polls for them (tests / TSan of the io loops' asynchronous tick path)
-        aeng_ = new AsyncCpuEngine(cfg_.tags, cfg_.tag_classes);
+        aeng_ = new AsyncCpuEngine(cfg_.tags, cfg_.tag_classes, cfg_.tag_unicode);
         eng_.reset(aeng_);
       } else {
-        eng_.reset(new CpuEngine(cfg_.tags, cfg_.tag_classes));
+        eng_.reset(new CpuEngine(cfg_.tags, cfg_.tag_classes, cfg_.tag_unicode));
       }
-      if (cfg_.verify) ver_.reset(new Verifier(cfg_.tags, cfg_.tag_classes));
+      if (cfg_.verify) ver_.reset(new Verifier(cfg_.tags, cfg_.tag_classes, cfg_.tag_unicode));
     }
   }
 
@@ -3523,7 +3523,7 @@ class Loop {
     const char* e = env_get("QMX_LOOP_REQ_CHECK");
     return !e || atoi(e) != 0;
   }();
-  TagSet ts_ = make_tagset(cfg_.tags, cfg_.tag_classes);
+  TagSet ts_ = make_tagset(cfg_.tags, cfg_.tag_classes, cfg_.tag_unicode);
   bool kick_ = false;
   std::mutex rmu_;
   std::vector<ResultBatch> rq_;
@@ -3721,7 +3721,9 @@ int run_server(const ServerCfg& cfg0) {
   // A class tag set (runtime.native_regex_tags) takes loop ticks like a literal one: its grid
   // is made with the flag and launches the kernel that carries the class paths
   // (qmx_ctick_persistent); the loops' engines carry the same tag set, so they pair with it.
-  const bool cls_tags = cfg.tag_classes && tag_classes(make_tagset(cfg.tags, true)) != nullptr;
+  // (a pair tag set, runtime.native_unicode_tags, is of the class kind: its text is folded on read)
+  const bool cls_tags = (cfg.tag_classes || cfg.tag_unicode) &&
+                        tag_classes(make_tagset(cfg.tags, cfg.tag_classes, cfg.tag_unicode)) != nullptr;
   const bool loop_ticks = hip && cfg.tick_mode != "lanes" && cfg.shared_engine != 1;
   const bool shared = !loop_ticks && (cfg.shared_engine < 0 ? hip : cfg.shared_engine > 0);
   if (shared) hub.reset(new GpuHub(cfg, (int)loops.size()));

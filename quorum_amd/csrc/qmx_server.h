@@ -59,6 +59,7 @@ struct ServerCfg {
   bool hide_intermediate = true, hide_final = false, skip_final = false, suppress = false;
   std::vector<std::string> tags;
   bool tag_classes = false;  // runtime.native_regex_tags: class tags ("." / "[...]") run natively
+  bool tag_unicode = false;  // runtime.native_unicode_tags: non-ASCII tags (uncased / simple case pairs) run natively
   // strategy.aggregate (consulted whatever strategy is selected, as in quorum)
   std::string aggregator_name;  // empty = none
   std::string prompt_template, intermediate_separator, query_format, source_label_format;

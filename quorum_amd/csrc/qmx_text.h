@@ -40,6 +40,7 @@ constexpr int kJsonMaxDepth = 256;  // deeper == RecursionError (stream abort)
 // as its lowercase byte and a class element as 0x80 + its index into TagClasses (pattern bytes
 // are otherwise printable ASCII), len[] counts elements.
 constexpr int kMaxClasses = 32;
+constexpr int kMaxFold = 32;  // distinct pair characters of a pair tag set
 enum : uint8_t { CLS_WIDE = 1, CLS_DOT = 2 };  // accepts non-ASCII code points / is a '.'
 struct TagClasses {
   int n;                               // distinct class definitions
@@ -47,6 +48,14 @@ struct TagClasses {
   uint8_t flags[kMaxClasses];
   int srclen[kMaxTags];
   uint8_t src[kMaxTags][kMaxTagLen + 1];  // the tag's lowercased source text (depth-0 holdback)
+  // Pair tag sets (make_tagset(tags, classes, unicode = true), a non-ASCII cased character in
+  // a tag): the tags are literal — n == 0, name[] holds the UTF-8 bytes of the lowercased tag —
+  // and the text is folded as it is read: the upper member of a pair stands for its lower
+  // member (same byte length).  A character's bytes are packed little-endian, byte k at bit 8k.
+  int nfold;                           // distinct pair characters of the tags; 0: a class tag set
+  int span;                            // bytes of the longest pattern
+  uint8_t fold_len[kMaxFold];
+  uint32_t fold_up[kMaxFold], fold_lo[kMaxFold];
 };
 
 // (The layout of TagSet is the literal tag sets': the kernels keep a copy in LDS.  A class
@@ -58,7 +67,8 @@ struct TagSet {
   int len[kMaxTags];
   uint8_t name[kMaxTags][kMaxTagLen + 1];  // lowercase ASCII (class tags: see TagClasses)
 };
-// 0: a literal tag set; else some tag has a class element or an escape
+// 0: a literal tag set; else some tag has a class element or an escape, or (a pair tag set)
+// a non-ASCII cased character
 QMX_HD int tagset_cls_id(const TagSet& ts) { return ts.name[0][kMaxTagLen]; }
 
 QMX_HD uint8_t lower_ascii(uint8_t c) { return (c >= 'A' && c <= 'Z') ? (uint8_t)(c + 32) : c; }
@@ -243,6 +253,70 @@ QMX_HD bool source_prefix(const R& x, int q, int n, const TagSet& ts, const TagC
       ok = lower_ascii(x[q + i]) == want;
     }
     if (ok) return true;
+  }
+  return false;
+}
+
+// ---------------------------------------------------------------------------
+// pair tags: literal patterns, the text folded on read (tc.nfold > 0)
+// ---------------------------------------------------------------------------
+// Walk pattern `pat` over x[p:n), every character of the text as the patterns see it: an ASCII
+// letter lowercased, the upper member of a pair replaced by its lower member.  Both have the
+// same byte length, so the text and the pattern move together.  1: it matches (the token ends
+// at p + pattern_len);  0: mismatch;  -1: every byte of x[p:n) matched and the text ended
+// before the pattern did (a character cut short at n is a prefix of its folded self).
+template <class R>
+QMX_HD int fold_walk(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, int pat) {
+  const int P = pattern_len(ts, pat);
+  for (int i = 0; i < P;) {
+    if (p + i >= n) return -1;
+    const uint8_t c = x[p + i];
+    if (c < 0xC0) {  // ASCII (a stray continuation byte equals no pattern byte here)
+      if (lower_ascii(c) != pattern_byte(ts, pat, i)) return 0;
+      ++i;
+      continue;
+    }
+    const int ln = c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : 2;
+    if (i + ln > P) return 0;
+    const int av = ln < n - (p + i) ? ln : n - (p + i);
+    uint32_t have = 0, want = 0;
+    for (int k = 0; k < av; ++k) have |= (uint32_t)x[p + i + k] << (8 * k);
+    for (int k = 0; k < ln; ++k) want |= (uint32_t)pattern_byte(ts, pat, i + k) << (8 * k);
+    const uint32_t m = av >= 4 ? 0xffffffffu : ((1u << (8 * av)) - 1u);
+    if (have != (want & m)) {
+      bool ok = false;
+      for (int f = 0; f < tc.nfold; ++f)
+        ok = ok || (tc.fold_len[f] == ln && (tc.fold_up[f] & m) == have && tc.fold_lo[f] == want);
+      if (!ok) return 0;
+    }
+    if (av < ln) return -1;
+    i += ln;
+  }
+  return 1;
+}
+
+// match_at for a pair tag set (a folded text matches at most one of the distinct tags)
+template <class R>
+QMX_HD int fold_match_at(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, int* tok_len) {
+  if (x[p] != '<') return 0;
+  const bool close = (p + 1 < n && x[p + 1] == '/');
+  for (int t = 0; t < ts.n; ++t) {
+    const int pat = close ? ts.n + t : t;
+    if (fold_walk(x, n, p, ts, tc, pat) == 1) {
+      *tok_len = pattern_len(ts, pat);
+      return close ? -(t + 1) : (t + 1);
+    }
+  }
+  return 0;
+}
+
+// pattern_prefix for a pair tag set
+template <class R>
+QMX_HD bool fold_pattern_prefix(const R& x, int q, int n, const TagSet& ts, const TagClasses& tc, bool opens_only) {
+  const int npat = opens_only ? ts.n : 2 * ts.n;
+  for (int pat = 0; pat < npat; ++pat) {
+    if (n - q > pattern_len(ts, pat)) continue;
+    if (fold_walk(x, n, q, ts, tc, pat) != 0) return true;
   }
   return false;
 }

@@ -60,7 +60,16 @@ _PLAIN_TAG = re.compile(r"^[ -~]+$")
 _NOT_PLAIN = set(".^$*+?{}[]\\|()<>/")
 
 
-def native_tag_ok(tags: Sequence[str], max_tags: int = 16, max_len: int = 61, classes: bool = False) -> bool:
+def _unicode_tag_chars_ok(tags: Sequence[str]) -> bool:
+    """No control, surrogate or unassigned code point in a tag (the C++ table knows the case
+    rule only: every code point it does not list is uncased to it)."""
+    import unicodedata
+
+    return all(unicodedata.category(c) not in ("Cn", "Cs", "Cc") for t in tags for c in t)
+
+
+def native_tag_ok(tags: Sequence[str], max_tags: int = 16, max_len: int = 61, classes: bool = False,
+                  unicode: bool = False) -> bool:
     """Tags the native/GPU matchers run exactly (qmx_text.h): literal printable ASCII, at
     most 16 distinct (lowercased) tags of at most 61 bytes — the MFMA matcher compares a
     16-byte window per '<' and the tail of longer patterns, two 16-pattern column blocks.
@@ -68,16 +77,23 @@ def native_tag_ok(tags: Sequence[str], max_tags: int = 16, max_len: int = 61, cl
 
     ``classes`` (``runtime.native_regex_tags``): also the class tags — '.', bracket classes
     and escaped punctuation after a literal first element.  The C++ parser (``make_tagset``)
-    is the one definition of that subset, so it is asked."""
+    is the one definition of that subset, so it is asked.
+
+    ``unicode`` (``runtime.native_unicode_tags``): also non-ASCII tags whose characters are
+    uncased or one of a simple case pair (é/É, я/Я); the C++ parser holds the table
+    (``qmx_unicode_fold.h``), the categories no tag may hold (Cn, Cs, Cc) are checked here."""
     low = {t.lower() for t in tags}
     if (0 < len(low) <= max_tags
             and all(_PLAIN_TAG.match(t) and not (set(t) & _NOT_PLAIN) and len(t) <= max_len for t in low)):
         return True
-    if not classes or max_tags != 16 or max_len != 61:
+    if not (classes or unicode) or max_tags != 16 or max_len != 61:
+        return False
+    if unicode and not _unicode_tag_chars_ok([str(t) for t in tags]):
         return False
     from . import native
 
-    return native.available() and bool(native.require().tagset_ok([str(t) for t in tags], True))
+    return native.available() and bool(native.require().tagset_ok([str(t) for t in tags], bool(classes),
+                                                                  bool(unicode)))
 
 
 class PyEngine:
@@ -183,12 +199,14 @@ def make_engine(kind: str, tags: Sequence[str], device: Optional[int] = None, **
     ``kind``: "auto" | "hip" | "cpu" | "python".  "hip" raises loudly when the HIP
     extension or a GPU is missing (no silent fallback on a GPU box).  ``opts`` go to the
     native engine as they are; a ``grid`` among them must be of the tag set's kind
-    (``native.make_grid(tags, ..., classes=classes)``: the class grid for a class tag set).
+    (``native.make_grid(tags, ..., classes=classes, unicode=unicode)``: the class grid for a
+    class tag set and for a pair tag set).
     """
     tags = list(tags)
     classes = bool(opts.pop("classes", False))
-    if kind == "python" or not native_tag_ok(tags, classes=classes):
-        if kind in ("hip", "cpu") and not native_tag_ok(tags, classes=classes):
+    unicode = bool(opts.pop("unicode", False))
+    if kind == "python" or not native_tag_ok(tags, classes=classes, unicode=unicode):
+        if kind in ("hip", "cpu") and not native_tag_ok(tags, classes=classes, unicode=unicode):
             logger.warning("thinking_tags %r need regex semantics: using the python engine", tags)
         return _py_engine(tags)
     from . import native  # noqa: WPS433 - heavy import deferred
@@ -199,10 +217,14 @@ def make_engine(kind: str, tags: Sequence[str], device: Optional[int] = None, **
             return _py_engine(tags)
         kind = "hip" if native.gpu_available() else "cpu"
     # (class tags keep their case in the key: "[Z-a]" and "[z-a]" are different patterns)
-    key = ((kind, classes) if classes else kind, tuple(t if classes else t.lower() for t in tags),
+    # (so do tags that may be non-ASCII: the C++ parser lowercases them through its pair table)
+    asis = classes or unicode
+    key = ((kind, classes, unicode) if asis else kind, tuple(t if asis else t.lower() for t in tags),
            -1 if device is None else device)
     eng = _NATIVE_CACHE.get(key)
     if eng is None:
+        if unicode:
+            opts["unicode"] = True
         eng = native.NativeEngine(kind, tags, device=device, classes=classes, **opts)
         _NATIVE_CACHE[key] = eng
     return eng

@@ -51,10 +51,14 @@ def gpu_available() -> bool:
         return False
 
 
-def strip_fn(tags: Sequence[str], classes: bool = False) -> Callable[[str, bool], str]:
+def strip_fn(tags: Sequence[str], classes: bool = False, unicode: bool = False) -> Callable[[str, bool], str]:
     ext = require()
-    # class tags go down as written: lowercasing would turn "[Z-a]" into another pattern
-    stripper = ext.Stripper(list(tags), classes=True) if classes else ext.Stripper([t.lower() for t in tags])
+    # class tags go down as written: lowercasing would turn "[Z-a]" into another pattern (and
+    # non-ASCII tags are lowercased by the C++ parser, through its pair table)
+    if classes or unicode:
+        stripper = ext.Stripper(list(tags), classes=bool(classes), unicode=bool(unicode))
+    else:
+        stripper = ext.Stripper([t.lower() for t in tags])
 
     def _strip(text, on):
         if not on:
@@ -67,12 +71,13 @@ def strip_fn(tags: Sequence[str], classes: bool = False) -> Callable[[str, bool]
 
 
 def make_grid(tags: Sequence[str], device: int, doors: int, wg_per_door: int = 8, idle_ms: int = 50,
-              classes: bool = False):
+              classes: bool = False, unicode: bool = False):
     """A multi-door loop-tick grid (``HipGrid``) of the kind this tag set's engines need: the
-    class kernel for a class tag set (``classes`` on and a '.' or bracket class in a tag), the
-    literal kernel otherwise.  Every ``NativeEngine`` given the grid must use the same tags."""
+    class kernel for a class tag set (``classes`` on and a '.' or bracket class in a tag) and
+    for a pair tag set (``unicode`` on and a cased non-ASCII character in a tag), the literal
+    kernel otherwise.  Every ``NativeEngine`` given the grid must use the same tags."""
     ext = require()
-    cls = bool(classes) and ext.tagset_has_classes(list(tags), True)
+    cls = bool(classes or unicode) and ext.tagset_has_classes(list(tags), bool(classes), bool(unicode))
     return ext.HipGrid(device, doors, wg_per_door, idle_ms, classes=cls)
 
 
@@ -81,16 +86,18 @@ class NativeEngine:
 
     def __init__(self, kind: str, tags: Sequence[str], device: Optional[int] = None,
                  tile_bytes: int = 16384, max_slots: int = 8192, content_cap: int = 1 << 20, lanes: int = 1,
-                 grid=None, door: int = -1, ndoors: int = 1, classes: bool = False):
+                 grid=None, door: int = -1, ndoors: int = 1, classes: bool = False, unicode: bool = False):
         ext = require()
         self.kind = kind
         self.name = kind
         self.tags: List[str] = list(tags)
         self.classes = bool(classes)
+        self.unicode = bool(unicode)
         low = []
         for t in tags:
             # class tags go down as written: lowercasing would turn "[Z-a]" into another pattern
-            t = t if classes else t.lower()
+            # (non-ASCII tags too: the C++ parser lowercases them through its pair table)
+            t = t if classes or unicode else t.lower()
             if t not in low:
                 low.append(t)
         if kind == "hip":
@@ -101,10 +108,10 @@ class NativeEngine:
             # grid: a HipGrid (loop ticks) — this engine posts its ticks into door `door` of it.
             # A class tag set needs a grid made with classes=True (make_grid picks the kind)
             self._e = ext.HipEngine(low, device, tile_bytes, max_slots, content_cap, lanes, grid, door, ndoors,
-                                     classes=self.classes)
+                                     classes=self.classes, unicode=self.unicode)
             self.offload = True
         else:
-            self._e = ext.CpuEngine(low, classes=self.classes)
+            self._e = ext.CpuEngine(low, classes=self.classes, unicode=self.unicode)
             self.offload = False
         self.open = self._e.open
         self.feed = self._e.feed

@@ -6,7 +6,9 @@
 //    content and finals whether a stream is fed in one piece or split at random points with
 //    ticks at random moments (the tile/carry/holdback logic of every split point) — with the
 //    default tags and with class tag sets ('.', "[...]", escapes: make_tagset(tags, true)),
-//    their pieces including multi-byte code points and '<' / '>' at class positions;
+//    their pieces including multi-byte code points and '<' / '>' at class positions, and with
+//    non-ASCII tag sets (make_tagset(tags, false, true): uncased and case-pair characters, the
+//    text folded on read), their pieces in both cases, look-alikes and JSON-escaped forms;
 //  * strip_final idempotence on already-stripped text and JSON DOM round-trips
 //    (parse(dump(parse(x))) == parse(x)), py_float_repr/escape on random inputs;
 //  * everything runs under -fsanitize=address,undefined: any OOB / UB aborts the run.
@@ -37,6 +39,7 @@ const char* kPieces[] = {"<think>", "</think>", "<THINK>", "</Think>", "<reason>
 struct ClassSet {
   std::vector<std::string> tags;
   std::vector<const char*> pieces;
+  bool unicode = false;  // a non-ASCII tag set (make_tagset's `unicode`), no class tags
 };
 const ClassSet kClassSets[] = {
     {{"think", "th.nk"},
@@ -47,6 +50,16 @@ const ClassSet kClassSets[] = {
       "<ndte>", "<xQz>", "</x\xc3\xa9z>", "<x<z>", "<x>z>", "<xyz>", "<x\\nz>", "</x", "z>"}},
     {{"a.", "a", "q[^a-z]"},
      {"<a>", "<a>>", "</a>>", "</a>", "<aX>", "</A\xe4\xb8\xad>", "<q1>", "</q\xf0\x9f\x98\x80>", "<qa>", "<q<>", "<q", "<a"}},
+    // a pair tag set (réflexion, я, 𐐨x) with the uncased 思考
+    {{"think", "réflexion", "я", "𐐨x", "思考"},
+     {"<réflexion>", "</RÉFLEXION>", "<R\\u00c9flexion>", "<rèflexion>", "<RÉ", "flexion>", "<я>", "</Я>", "<ю>", "<\\u042f>",
+      "<𐐀X>", "</𐐨x>", "<\\ud801\\udc00x>", "<\\ud801", "\\udc00x>", "<思考>", "</\\u601d\\u8003>", "<思", "考>", "<怞考>",
+      "<think>", "</THINK>"},
+     true},
+    // an uncased (literal) set with a pattern past the 16-byte window
+    {{"思考", "a思考过程分"},
+     {"<思考>", "</思考>", "<a思考过程分>", "</A思考过程分>", "</a思考过程切>", "<a思考", "过程分>", "<\\u601d", "\\u8003>"},
+     true},
 };
 const ClassSet* g_class = nullptr;  // the class tag set of this iteration (null: the default tags)
 
@@ -88,7 +101,7 @@ struct Run {
 
 Run run_engine(const std::vector<std::string>& tags, const std::vector<std::string>& bodies,
                const std::vector<bool>& filt, bool split) {
-  CpuEngine eng(tags, g_class != nullptr);
+  CpuEngine eng(tags, g_class != nullptr && !g_class->unicode, g_class != nullptr && g_class->unicode);
   Run out;
   std::vector<int> slots;
   for (size_t i = 0; i < bodies.size(); ++i) slots.push_back(eng.open((int)i, filt[i], true));
@@ -202,7 +215,7 @@ int main(int argc, char** argv) {
       if (++fails <= 3) fprintf(stderr, "streaming invariance violated (iteration %d)\n", it);
     }
     // strip_final: stripping a stripped text (no tags left in it) only re-strips whitespace
-    TagSet ts = make_tagset(tags, g_class != nullptr);
+    TagSet ts = make_tagset(tags, g_class != nullptr && !g_class->unicode, g_class != nullptr && g_class->unicode);
     std::string t = rand_content() + rand_content();
     std::string s1 = strip_final(ts, (const uint8_t*)t.data(), t.size());
     std::string s2 = strip_final(ts, (const uint8_t*)s1.data(), s1.size());

@@ -287,6 +287,14 @@ class RuntimeConfig:
                tag with a regex metacharacter sends the streams to the python engine and
                keeps the native server from starting.  Tags outside that subset (quantifiers,
                groups, anchors, "|", shorthands) are refused either way
+    native_unicode_tags: run non-ASCII thinking tags ("思考", "réflexion") on the native engines.
+               A tag may hold uncased characters (CJK, kana, hangul, emoji) and characters of a
+               simple case pair (é/É, я/Я: two code points of one UTF-8 length that fold onto
+               each other and onto nothing else); the text is folded as it is read, so
+               "<RÉFLEXION>" opens "réflexion".  Characters with a wider case relation (ω, σ, µ,
+               ß, ı, İ, å, combining marks of case expansions), control and unassigned code
+               points, and a tag set that also has a class tag are refused: those still need the
+               python engine.  Off (the default): any non-ASCII tag does
     """
 
     engine: str = "auto"
@@ -311,10 +319,13 @@ class RuntimeConfig:
     read_pace_us: int = 50
     light_host_sessions: Optional[int] = None
     native_regex_tags: bool = False
+    native_unicode_tags: bool = False
 
     def __post_init__(self):
         if not isinstance(self.native_regex_tags, bool):
             raise ValueError(f"runtime.native_regex_tags must be true or false, got {self.native_regex_tags!r}")
+        if not isinstance(self.native_unicode_tags, bool):
+            raise ValueError(f"runtime.native_unicode_tags must be true or false, got {self.native_unicode_tags!r}")
 
     @classmethod
     def from_config(cls, cfg: Dict[str, Any]) -> "RuntimeConfig":

@@ -15,15 +15,17 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def mock_stream(tokens=20, think=True):
+def mock_stream(tokens=20, think=True, tag="think"):
+    """tag: the think block's tag as the upstream writes it (--body-tag, e.g. RÉFLEXION)."""
     def ev(delta, finish="null"):
         return ('data: {"id": "chatcmpl-mock", "object": "chat.completion.chunk", "created": 1700000000, '
                 '"model": "mock", "choices": [{"index": 0, "delta": %s, "finish_reason": %s}]}\n\n'
                 % (delta, finish)).encode()
     out = [ev('{"role": "assistant", "content": ""}')]
     if think:
-        out += [ev('{"content": "<thi"}'), ev('{"content": "nk>let me reason about the request"}'),
-                ev('{"content": " carefully before answering</th"}'), ev('{"content": "ink>"}')]
+        a, b = tag[:3], tag[3:]
+        out += [ev('{"content": "<%s"}' % a), ev('{"content": "%s>let me reason about the request"}' % b),
+                ev('{"content": " carefully before answering</%s"}' % tag[:2]), ev('{"content": "%s>"}' % tag[2:])]
     words = ["The", " quick", " brown", " fox", " jumps", " over", " the", " lazy", " dog", "."]
     out += [ev('{"content": "%s"}' % words[i % 10]) for i in range(tokens)]
     out += [ev("{}", '"stop"'), b"data: [DONE]\n\n"]
@@ -67,10 +69,16 @@ def main():
                     help="class tags ('.', '[...]': runtime.native_regex_tags), e.g. --tags think,th.nk: one-shot "
                          "launches (qmx_ctick_kernel), or with --grid N a class grid (HipGrid classes=True, "
                          "qmx_ctick_persistent)")
+    ap.add_argument("--unicode", action="store_true",
+                    help="non-ASCII tags (runtime.native_unicode_tags), e.g. --tags think,思考 (a literal tag set: "
+                         "the literal kernels) or --tags think,réflexion (a pair tag set: the class kernels, with "
+                         "--grid N a class grid)")
+    ap.add_argument("--body-tag", default="think",
+                    help="mock shape: the think block's tag as the upstream writes it, e.g. réflexion or RÉFLEXION")
     args = ap.parse_args()
     from quorum_amd.ops.native import NativeEngine
 
-    body = mock_stream() if args.shape == "mock" else tagdense_stream()
+    body = mock_stream(tag=args.body_tag) if args.shape == "mock" else tagdense_stream()
     tags = args.tags.split(",")
     results = []
     grid = None
@@ -79,13 +87,17 @@ def main():
 
         ext = native.require()
         # a class tag set runs on a grid of its own kind (the class kernel)
-        grid = ext.HipGrid(0, args.grid, 8, classes=args.classes and ext.tagset_has_classes(tags, True))
+        # (so does a pair tag set: --unicode and a cased non-ASCII character in a tag)
+        grid = ext.HipGrid(0, args.grid, 8, classes=(args.classes or args.unicode)
+                           and ext.tagset_has_classes(tags, args.classes, args.unicode))
     combos = {"ft": (True, True), "f": (True, False), "t": (False, True)}
     for filt, emit in [combos[c] for c in args.combos.split(",")]:
         for n in [int(x) for x in args.slots.split(",")]:
             kw = {"grid": grid, "door": 0} if grid is not None else {}
             if args.classes:
                 kw["classes"] = True
+            if args.unicode:
+                kw["unicode"] = True
             eng = NativeEngine(args.engine, tags, device=0, max_slots=4096, content_cap=1 << 16, **kw)
             walls = []
             evs = [e + b"\n\n" for e in body.split(b"\n\n") if e]
@@ -111,6 +123,10 @@ def main():
                    "wall_us_min": round(1e6 * walls[0], 1)}
             if st:
                 rec["kernel_us_avg"] = round(1000 * st["kernel_ms"] / max(st["launches"], 1), 1)
+                # per-item span and post -> done per tick (profiles/class_tags/NOTES.md's other two figures)
+                rec["item_us_avg"] = round(st.get("item_us", 0.0) / max(st["launches"], 1), 2)
+                rec["post_done_us_avg"] = round(st.get("gpu_wait_us", 0.0) / max(st["launches"], 1), 1)
+                rec["escalations"] = st.get("escalations")
                 if st.get("stage_items"):
                     ni = st["stage_items"]
                     rec["stage_us_per_item"] = {k: round(v / ni, 2) for k, v in st.items()
