@@ -23,13 +23,12 @@ using namespace qmx;
 namespace {
 
 struct PyStreamFilter {
-  TagSet ts;
+  Tags tags;
   FilterState fs;
-  PyStreamFilter(const std::vector<std::string>& tags, bool classes, bool unicode)
-      : ts(make_tagset(tags, classes, unicode)) {}
+  PyStreamFilter(const std::vector<std::string>& t, bool classes, bool unicode) : tags(make_tags(t, classes, unicode)) {}
   py::bytes feed(const std::string& s) {
     std::string out;
-    filter_feed(ts, fs, (const uint8_t*)s.data(), s.size(), out);
+    filter_feed(tags, fs, (const uint8_t*)s.data(), s.size(), out);
     return py::bytes(out);
   }
   py::bytes flush() {
@@ -39,9 +38,9 @@ struct PyStreamFilter {
 };
 
 struct PyStripper {
-  TagSet ts;
-  PyStripper(const std::vector<std::string>& tags, bool classes, bool unicode) : ts(make_tagset(tags, classes, unicode)) {}
-  py::bytes strip(const std::string& s) { return py::bytes(strip_final(ts, (const uint8_t*)s.data(), s.size())); }
+  Tags tags;
+  PyStripper(const std::vector<std::string>& t, bool classes, bool unicode) : tags(make_tags(t, classes, unicode)) {}
+  py::bytes strip(const std::string& s) { return py::bytes(strip_final(tags, (const uint8_t*)s.data(), s.size())); }
 };
 
 py::tuple tick_to_py(HostEngine& e, int64_t created, int lane = 0, std::vector<int>* taken = nullptr,
@@ -485,27 +484,27 @@ PYBIND11_MODULE(_qmx, m) {
       .def(py::init<const std::vector<std::string>&, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
            py::arg("unicode") = false)
       .def("strip", &PyStripper::strip);
-  // is this tag list inside what make_tagset runs natively (the one definition of the subset)?
+  // is this tag list inside what make_tags runs natively (the one definition of the subset)?
   m.def("tagset_ok", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
     try {
-      make_tagset(tags, classes, unicode);
+      make_tags(tags, classes, unicode);
       return true;
     } catch (const std::invalid_argument&) {
       return false;
     }
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
-  // why make_tagset refuses this tag list ("" when it does not): the limit's own message
+  // why make_tags refuses this tag list ("" when it does not): the limit's own message
   m.def("tagset_error", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
     try {
-      make_tagset(tags, classes, unicode);
+      make_tags(tags, classes, unicode);
       return std::string();
     } catch (const std::invalid_argument& e) {
       return std::string(e.what());
     }
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
-  // distinct tags of the set make_tagset builds ("É" and "é" are one)
+  // distinct tags of the set make_tags builds ("É" and "é" are one)
   m.def("tagset_size", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
-    return make_tagset(tags, classes, unicode).n;
+    return make_tags(tags, classes, unicode).ts.n;
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
   // the case rule of one non-ASCII tag character (qmx_unicode_fold.h): (kind, partner) with
   // kind 0 uncased, 1 a simple case pair, 2 refused; partner: the pair's other member, else cp
@@ -514,23 +513,25 @@ PYBIND11_MODULE(_qmx, m) {
     const int kind = unicode_tag_char(cp, &low);
     return py::make_tuple(kind, kind == 1 ? unicode_tag_partner(cp) : cp);
   });
-  // does this tag list make a class tag set (a '.', a bracket class)?  The test HipEngine uses
-  // to pair an engine with a grid: a class tag set needs HipGrid(classes=True)
-  // (a pair tag set — `unicode` and a cased non-ASCII character in a tag — is of that kind too)
+  // the kind of the tag set this list makes (qmx_text.h TagKind)
+  m.def("tagset_kind", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
+    const TagKind k = make_tags(tags, classes, unicode).kind;
+    return k == TAGS_PAIR ? "pair" : k == TAGS_CLASS ? "class" : "literal";
+  }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
+  // of the class kind (class or pair)?  Such a tag set's engines need HipGrid(classes=True)
   m.def("tagset_has_classes", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
-    return tag_classes(make_tagset(tags, classes, unicode)) != nullptr;
+    return make_tags(tags, classes, unicode).kind != TAGS_LITERAL;
   }, py::arg("tags"), py::arg("classes") = true, py::arg("unicode") = false);
   // candidates '<' of `text` the GPU kernels would hand to the host path (qmx_text.h
   // class_candidate, the shared suspect rule), with the streaming or the strip tables
   m.def("class_suspects", [](const std::vector<std::string>& tags, const std::string& text, bool strip) {
-    const TagSet ts = make_tagset(tags, true);
+    const Tags t = make_tags(tags, true);
     int k = 0;
-    const TagClasses* tc = tag_classes(ts);
-    if (tc == nullptr) return k;
+    if (t.kind == TAGS_LITERAL) return k;
     const uint8_t* x = (const uint8_t*)text.data();
     for (int p = 0; p < (int)text.size(); ++p) {
       int tok = 0, len = 0;
-      if (x[p] == '<' && class_candidate(x, (int)text.size(), p, ts, *tc, strip, &tok, &len) == CC_SUSPECT) ++k;
+      if (x[p] == '<' && class_candidate(x, (int)text.size(), p, t.ts, t.tc, strip, &tok, &len) == CC_SUSPECT) ++k;
     }
     return k;
   }, py::arg("tags"), py::arg("text"), py::arg("strip") = false);
@@ -538,7 +539,7 @@ PYBIND11_MODULE(_qmx, m) {
   py::class_<CpuEngine> ce(m, "CpuEngine");
   ce.def(py::init([](const std::vector<std::string>& tags, bool classes, bool unicode) {
            env_refresh();
-           return new CpuEngine(tags, classes, unicode);
+           return new CpuEngine(make_tags(tags, classes, unicode));
          }),
          py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
   bind_engine(ce);
@@ -587,8 +588,8 @@ PYBIND11_MODULE(_qmx, m) {
   he.def(py::init([](const std::vector<std::string>& tags, int device, int tile, int max_slots, int content_cap,
                       int lanes, HipGrid* grid, int door, int ndoors, bool classes, bool unicode) {
            env_refresh();
-           return new HipEngine(tags, device, tile, max_slots, content_cap, lanes, grid, door, ndoors, classes,
-                                unicode);
+           return new HipEngine(make_tags(tags, classes, unicode), device, tile, max_slots, content_cap, lanes, grid,
+                                door, ndoors);
          }),
          py::arg("tags"), py::arg("device"), py::arg("tile_bytes") = 16384, py::arg("max_slots") = 8192,
          py::arg("content_cap") = 1 << 20, py::arg("lanes") = 1, py::arg("grid") = nullptr, py::arg("door") = -1,

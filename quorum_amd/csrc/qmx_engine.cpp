@@ -113,12 +113,6 @@ bool parse_class_tag(const std::string& t, std::vector<Elem>& out) {
   return !out.empty() && !out[0].cls;
 }
 
-// the TagClasses of every class tag set this process has made (TagSet keeps the id + 1)
-constexpr int kClsPool = 255;
-std::mutex cls_mu;
-TagClasses* cls_pool[kClsPool];
-int cls_n = 0;
-
 }  // namespace
 
 // The case rule of a non-ASCII tag character (qmx_unicode_fold.h, generated from the rule in
@@ -147,11 +141,11 @@ uint32_t unicode_tag_partner(uint32_t cp) {
   return cp;
 }
 
-TagSet make_tagset(const std::vector<std::string>& tags, bool classes, bool unicode) {
-  TagSet ts;
-  std::memset(&ts, 0, sizeof(ts));
-  TagClasses tc;
-  std::memset(&tc, 0, sizeof(tc));
+Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode) {
+  Tags out;
+  std::memset(&out, 0, sizeof(out));
+  TagSet& ts = out.ts;
+  TagClasses& tc = out.tc;
   bool any_cls = false, any_wide = false;
   std::vector<std::string> seen;
   auto pack = [](uint32_t cp, int* len) {  // UTF-8 bytes, byte k at bit 8k
@@ -261,34 +255,18 @@ TagSet make_tagset(const std::vector<std::string>& tags, bool classes, bool unic
     throw std::invalid_argument("class tags and non-ASCII tags do not mix in one tag set (runs with --impl python)");
   if (tc.nfold > 0)
     for (int pat = 0; pat < 2 * ts.n; ++pat) tc.span = std::max(tc.span, pattern_len(ts, pat));
-  if (any_cls || tc.nfold > 0) {
-    // interned: TagSet is copied by value everywhere (kernel parameters included) and keeps
-    // only the id; the tables live for the process, one entry per distinct class tag set
-    std::lock_guard<std::mutex> g(cls_mu);
-    int id = 0;
-    for (int k = 0; k < cls_n && id == 0; ++k)
-      if (std::memcmp(cls_pool[k], &tc, sizeof(tc)) == 0) id = k + 1;
-    if (id == 0) {
-      if (cls_n >= kClsPool) throw std::invalid_argument("too many distinct class tag sets in one process");
-      cls_pool[cls_n] = new TagClasses(tc);
-      id = ++cls_n;
-    }
-    ts.name[0][kMaxTagLen] = (uint8_t)id;
-  }
-  return ts;
-}
-
-const TagClasses* tag_classes(const TagSet& ts) {
-  const int id = tagset_cls_id(ts);
-  if (id == 0) return nullptr;
-  std::lock_guard<std::mutex> g(cls_mu);
-  return cls_pool[id - 1];
+  out.kind = tc.nfold > 0 ? TAGS_PAIR : any_cls ? TAGS_CLASS : TAGS_LITERAL;
+  // (a literal tag set keeps no tables: its source text is its names)
+  if (out.kind == TAGS_LITERAL) std::memset(&tc, 0, sizeof(tc));
+  return out;
 }
 
 // --------------------------------------------------------------------------------
 // streaming filter: state (depth, tail); X = tail ++ text, token walk left to right
 // --------------------------------------------------------------------------------
-void filter_feed(const TagSet& ts, FilterState& fs, const uint8_t* text, size_t n, std::string& out) {
+void filter_feed(const Tags& tags, FilterState& fs, const uint8_t* text, size_t n, std::string& out) {
+  const TagSet& ts = tags.ts;
+  const TagClasses& tc = tags.tc;
   std::string xs;
   xs.reserve(fs.tail_len + n);
   xs.append((const char*)fs.tail, fs.tail_len);
@@ -297,16 +275,12 @@ void filter_feed(const TagSet& ts, FilterState& fs, const uint8_t* text, size_t 
   int N = (int)xs.size();
   int i = 0;
   fs.tail_len = 0;
-  const TagClasses* tc = tag_classes(ts);
-  const bool pair = tc != nullptr && tc->nfold > 0;  // literal tags, the text folded on read
-  const bool cls = tc != nullptr && !pair;
   while (true) {
     // next token at or after i (depth 0: opens only are tokens)
     int p = i, tok = 0, L = 0;
     for (; p < N; ++p) {
       if (x[p] != '<') continue;
-      tok = cls ? class_match_at(x, N, p, ts, *tc, false, &L)
-                : pair ? fold_match_at(x, N, p, ts, *tc, &L) : match_at(x, N, p, ts, &L);
+      tok = token_at(tags.kind, x, N, p, ts, tc, false, &L);
       if (tok > 0 || (tok < 0 && fs.depth > 0)) break;
       tok = 0;
     }
@@ -323,18 +297,16 @@ void filter_feed(const TagSet& ts, FilterState& fs, const uint8_t* text, size_t 
     // no more tokens: hold back a trailing partial tag from the LAST '<'
     int q = N - 1;
     bool hold;
-    if (cls && fs.depth > 0) {
+    if (tags.kind == TAGS_CLASS && fs.depth > 0) {
       // class tags inside a block: a class element may swallow a later '<', so keep from the
       // EARLIEST '<' whose rest is still a proper prefix of some pattern (the reference keeps
-      // its whole buffer here; the byte bound of make_tagset keeps this within kMaxTail)
+      // its whole buffer here; the byte bound of make_tags keeps this within kMaxTail)
       for (q = i; q < N; ++q)
-        if (x[q] == '<' && class_prefix(x, q, N, ts, *tc)) break;
+        if (x[q] == '<' && held_at(tags.kind, x, q, N, ts, tc, fs.depth)) break;
       hold = q < N;
     } else {
       while (q >= i && x[q] != '<') --q;
-      hold = q >= i && (cls ? source_prefix(x, q, N, ts, *tc)
-                            : pair ? fold_pattern_prefix(x, q, N, ts, *tc, fs.depth == 0)
-                                   : pattern_prefix(x, q, N, ts, fs.depth == 0));
+      hold = q >= i && held_at(tags.kind, x, q, N, ts, tc, fs.depth);
     }
     int cut = hold ? q : N;
     if (fs.depth == 0) out.append((const char*)x + i, cut - i);
@@ -393,9 +365,9 @@ static std::string strip_final_classes(const TagSet& ts, const TagClasses& tc, c
   return out.substr(a, b - a);
 }
 
-std::string strip_final(const TagSet& ts, const uint8_t* x, size_t n) {
-  const TagClasses* tc = tag_classes(ts);
-  if (tc != nullptr && tc->nfold == 0) return strip_final_classes(ts, *tc, x, (int)n);
+std::string strip_final(const Tags& tags, const uint8_t* x, size_t n) {
+  const TagSet& ts = tags.ts;
+  if (tags.kind == TAGS_CLASS) return strip_final_classes(ts, tags.tc, x, (int)n);
   // (a pair tag set: the tokens of the folded text — the backreference folds both sides, so a
   // close of the same tag in any case is the open's close, as for ASCII letters)
   struct Tok { int pos, len, id; };
@@ -403,7 +375,7 @@ std::string strip_final(const TagSet& ts, const uint8_t* x, size_t n) {
   for (int p = 0; p < (int)n; ++p) {
     if (x[p] != '<') continue;
     int L = 0;
-    int id = tc != nullptr ? fold_match_at(x, (int)n, p, ts, *tc, &L) : match_at(x, (int)n, p, ts, &L);
+    int id = token_at(tags.kind, x, (int)n, p, ts, tags.tc, true, &L);
     if (id != 0) toks.push_back({p, L, id});
   }
   std::vector<int> next_close(toks.size(), -1);
@@ -498,7 +470,7 @@ static bool str_body_ok(const uint8_t* x, int a, int b) {
   return utf8_valid(x, a, b);
 }
 
-static void handle_event(const TagSet& ts, SlotCore& s, const uint8_t* e, int m, int64_t created,
+static void handle_event(const Tags& tags, SlotCore& s, const uint8_t* e, int m, int64_t created,
                          std::string& out, std::string& scratch) {
   EvResult r;
   const int tp = (int)s.tpl_pre.size(), tsz = (int)s.tpl_suf.size();
@@ -524,7 +496,7 @@ static void handle_event(const TagSet& ts, SlotCore& s, const uint8_t* e, int m,
   c.resize((size_t)dl);
   json_unescape(e, r.str_a, r.str_b, (uint8_t*)&c[0]);
   scratch.clear();
-  if (s.filter) filter_feed(ts, s.fs, (const uint8_t*)c.data(), c.size(), scratch);
+  if (s.filter) filter_feed(tags, s.fs, (const uint8_t*)c.data(), c.size(), scratch);
   else scratch.assign(c);
   s.content += scratch;
   if (!scratch.empty() && s.emit) {
@@ -534,7 +506,7 @@ static void handle_event(const TagSet& ts, SlotCore& s, const uint8_t* e, int m,
   }
 }
 
-void process_slot(const TagSet& ts, SlotCore& s, const uint8_t* data, size_t n, bool eof, int64_t created,
+void process_slot(const Tags& tags, SlotCore& s, const uint8_t* data, size_t n, bool eof, int64_t created,
                   std::string& out) {
   if (s.aborted || s.done) return;
   s.carry.append((const char*)data, n);
@@ -566,7 +538,7 @@ void process_slot(const TagSet& ts, SlotCore& s, const uint8_t* data, size_t n, 
       from = j + 1;
       continue;
     }
-    handle_event(ts, s, x + pos, j - pos, created, out, scratch);  // leftmost separator
+    handle_event(tags, s, x + pos, j - pos, created, out, scratch);  // leftmost separator
     pos = from = j + 2;
   }
   if (s.aborted) {
@@ -574,7 +546,7 @@ void process_slot(const TagSet& ts, SlotCore& s, const uint8_t* data, size_t n, 
     return;
   }
   if (eof) {
-    if (pos < N) handle_event(ts, s, x + pos, N - pos, created, out, scratch);
+    if (pos < N) handle_event(tags, s, x + pos, N - pos, created, out, scratch);
     s.carry.clear();
     if (!s.aborted) s.done = true;
     return;
@@ -582,13 +554,13 @@ void process_slot(const TagSet& ts, SlotCore& s, const uint8_t* data, size_t n, 
   s.carry.erase(0, pos);
 }
 
-void finalize_texts(const TagSet& ts, const std::vector<std::string>& texts, const FinalizeReq& r,
+void finalize_texts(const Tags& tags, const std::vector<std::string>& texts, const FinalizeReq& r,
                     FinalizeRes& out) {
   out.id = r.id;
   std::vector<std::string> kept;
   for (const auto& t : texts) {
     if (t.empty()) continue;
-    kept.push_back(r.strip ? strip_final(ts, (const uint8_t*)t.data(), t.size()) : t);
+    kept.push_back(r.strip ? strip_final(tags, (const uint8_t*)t.data(), t.size()) : t);
   }
   if (r.texts) {
     out.kind = 2;
@@ -619,8 +591,7 @@ static double mono_s() {
   return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
-HostEngine::HostEngine(const std::vector<std::string>& tags, bool classes, bool unicode)
-    : ts_(make_tagset(tags, classes, unicode)) {
+HostEngine::HostEngine(const Tags& tags) : tags_(tags) {
   if (const char* pe = env_get("QMX_PIPELINE")) pipeline_ = atoi(pe) != 0;
 }
 
@@ -879,7 +850,7 @@ void CpuEngine::run_tick(std::vector<Work>& work, std::vector<FinalizeReq>& fin,
     SlotCore& c = core_[w.slot];
     bool was_closed = c.done || c.aborted;
     std::string out;
-    process_slot(ts_, c, (const uint8_t*)w.data.data(), w.data.size(), w.eof, created, out);
+    process_slot(tags_, c, (const uint8_t*)w.data.data(), w.data.size(), w.eof, created, out);
     int flags = (c.done ? RF_DONE : 0) | (c.aborted ? RF_ABORTED : 0);
     if (!out.empty() || (flags && !was_closed)) results.push_back({w.slot, std::move(out), flags});
   }
@@ -887,7 +858,7 @@ void CpuEngine::run_tick(std::vector<Work>& work, std::vector<FinalizeReq>& fin,
     std::vector<std::string> texts;
     for (int s : r.slots) texts.push_back(text(s));
     FinalizeRes fr;
-    finalize_texts(ts_, texts, r, fr);
+    finalize_texts(tags_, texts, r, fr);
     fres.push_back(std::move(fr));
   }
 }
@@ -902,8 +873,7 @@ struct AsyncCpuEngine::Done {
   std::atomic<bool> ready{false};
 };
 
-AsyncCpuEngine::AsyncCpuEngine(const std::vector<std::string>& tags, bool classes, bool unicode)
-    : CpuEngine(tags, classes, unicode) {
+AsyncCpuEngine::AsyncCpuEngine(const Tags& tags) : CpuEngine(tags) {
   th_ = std::thread([this] { run(); });
 }
 

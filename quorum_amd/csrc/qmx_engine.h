@@ -28,15 +28,21 @@ namespace qmx {
 
 enum ResultFlags : int { RF_DONE = 1, RF_ABORTED = 2, RF_ESCALATED = 4 };
 
+// A tag set as host code holds it: the kernels' TagSet, the tables of a class or pair tag set
+// (zero for a literal one) and its kind.  A plain value — every filter, stripper and engine
+// owns or shares one, nothing is looked up.
+struct Tags {
+  TagSet ts;
+  TagClasses tc;
+  TagKind kind;
+};
 // classes: also accept class tags ("." / "[...]" / escaped punctuation; qmx_text.h TagClasses)
 // unicode: also accept non-ASCII tags whose characters are uncased or one of a simple case
 // pair (qmx_unicode_fold.h); a tag set with a pair character is a pair tag set (TagClasses::nfold)
-TagSet make_tagset(const std::vector<std::string>& tags, bool classes = false, bool unicode = false);
+Tags make_tags(const std::vector<std::string>& tags, bool classes = false, bool unicode = false);
 // the case rule of a non-ASCII tag character: 0 uncased, 1 a pair (*lower: its lower member), 2 refused
 int unicode_tag_char(uint32_t cp, uint32_t* lower);
 uint32_t unicode_tag_partner(uint32_t cp);  // the other member of cp's pair (cp: none)
-// the class tables and source text of a class tag set (null for a literal one)
-const TagClasses* tag_classes(const TagSet& ts);
 
 struct FilterState {
   int depth = 0;
@@ -45,10 +51,10 @@ struct FilterState {
 };
 
 // Sequential streaming think filter: appends released bytes to `out`.
-void filter_feed(const TagSet& ts, FilterState& fs, const uint8_t* text, size_t n, std::string& out);
+void filter_feed(const Tags& tags, FilterState& fs, const uint8_t* text, size_t n, std::string& out);
 
 // Final strip: same-tag leftmost non-greedy removal + Unicode strip.
-std::string strip_final(const TagSet& ts, const uint8_t* x, size_t n);
+std::string strip_final(const Tags& tags, const uint8_t* x, size_t n);
 
 // SSE envelopes (json.dumps(ensure_ascii=True) of quorum's event dicts, oai_proxy.py:629-646, 847-860)
 void escape_append(const uint8_t* y, size_t n, std::string& out);
@@ -71,7 +77,7 @@ struct SlotCore {
 };
 
 // Process newly arrived bytes of one stream (sequential algorithm); appends SSE to out.
-void process_slot(const TagSet& ts, SlotCore& s, const uint8_t* data, size_t n, bool eof,
+void process_slot(const Tags& tags, SlotCore& s, const uint8_t* data, size_t n, bool eof,
                   int64_t created, std::string& out);
 
 // One deferred slot operation: io loops batch their feed / finish / release calls of an
@@ -166,7 +172,7 @@ class SlotTable {
 
 class HostEngine {
  public:
-  explicit HostEngine(const std::vector<std::string>& tags, bool classes = false, bool unicode = false);
+  explicit HostEngine(const Tags& tags);
   virtual ~HostEngine() = default;
 
   // returns the slot; *gen (optional) receives the slot's open generation (SlotResult::gen)
@@ -249,7 +255,7 @@ class HostEngine {
   virtual size_t content_size(int slot);
   virtual void set_remote_content(int slot, const std::string* bytes, size_t len, bool host_copied = false);
 
-  const TagSet& tagset() const { return ts_; }
+  const Tags& tags() const { return tags_; }
 
  protected:
   // engine-specific batch processing: the tick's stream work AND its finalize requests
@@ -275,7 +281,7 @@ class HostEngine {
     std::string incoming;
   };
 
-  TagSet ts_;
+  const Tags tags_;
   std::mutex mu_;
   // open() appends under mu_ while tick lanes index other slots outside the lock
   SlotTable<Meta> meta_;
@@ -291,8 +297,7 @@ class HostEngine {
 
 class CpuEngine : public HostEngine {
  public:
-  explicit CpuEngine(const std::vector<std::string>& tags, bool classes = false, bool unicode = false)
-      : HostEngine(tags, classes, unicode) {}
+  explicit CpuEngine(const Tags& tags) : HostEngine(tags) {}
   // pipelined lanes on the CPU: the whole tick runs in job_complete (exercises GpuHub's
   // pipelined loop without a GPU)
   bool pipelined() const override { return pipeline_; }
@@ -312,7 +317,7 @@ class CpuEngine : public HostEngine {
 // CPU and TSan suites, where no GPU is.
 class AsyncCpuEngine : public CpuEngine {
  public:
-  explicit AsyncCpuEngine(const std::vector<std::string>& tags, bool classes = false, bool unicode = false);
+  explicit AsyncCpuEngine(const Tags& tags);
   ~AsyncCpuEngine() override;
   bool async_jobs() const override { return true; }
   void job_post(Job& j) override;
@@ -332,7 +337,7 @@ class AsyncCpuEngine : public CpuEngine {
 };
 
 // Shared by both engines' host-side finalisation.
-void finalize_texts(const TagSet& ts, const std::vector<std::string>& texts, const FinalizeReq& r,
+void finalize_texts(const Tags& tags, const std::vector<std::string>& texts, const FinalizeReq& r,
                     FinalizeRes& out);
 
 }  // namespace qmx

@@ -100,8 +100,8 @@ struct KParams {
   int npat;
   int32_t pat_E[2 * kMaxTags];  // Σ_j m(q0²+q1²) over the window part of each pattern (match iff dot == -E)
   int32_t plen[2 * kMaxTags];   // pattern_len(ts, t), 0 past npat (a load with no dependence on ts.n)
-  // class tags (qmx_text.h TagClasses, in device memory; null for a literal tag set): the
-  // tables and source text, read only where a class tag set needs them.  (In what was padding
+  // class and pair tags (the engine's Tags::tc in device memory; null for a literal tag set):
+  // the tables and source text, read only where such a tag set needs them.  (In what was padding
   // before `code`: the parameters' layout is the literal tag sets'.)
   const TagClasses* cls;
   // byte → matcher code: 1..94 for the bytes that occur in patterns (letters folded), 95 for
@@ -312,9 +312,8 @@ struct TickLane {
 class HipEngine : public HostEngine {
  public:
   // grid: loop-tick mode — one lane whose ticks go to door `door` of a shared multi-door grid
-  HipEngine(const std::vector<std::string>& tags, int device, int tile_bytes, int max_slots, int content_cap,
-            int lanes = 1, HipGrid* grid = nullptr, int door = -1, int ndoors = 1, bool classes = false,
-            bool unicode = false);
+  HipEngine(const Tags& tags, int device, int tile_bytes, int max_slots, int content_cap, int lanes = 1,
+            HipGrid* grid = nullptr, int door = -1, int ndoors = 1);
   ~HipEngine() override;
   // loop-tick mode (the io loop drives its own ticks): has the posted job's every result been
   // published?  Never blocks.  expect_us: the job's expected remaining time (poll timing).

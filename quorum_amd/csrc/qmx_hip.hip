@@ -292,7 +292,7 @@ __device__ inline bool pattern_tail_ok(const uint8_t* Z, int Zn, int p, int t, c
 // Σ_j mask·(w_j²) − 2·w_j·p_j (per base-8 digit) == −E[pat]  <=>  Σ_j (w_j − p_j)² == 0 over
 // the pattern's first 16 bytes  <=>  the window equals them (all of a tag up to 13 bytes;
 // longer patterns then compare their tail).  Distinct tags never both match at
-// one '<' (make_tagset), so at most one column of a row survives.
+// one '<' (make_tags), so at most one column of a row survives.
 // PatCol: this lane's pattern column of each block (t = 16·blk + lane % 16) — its match value
 // −E and length — read from KParams once per tile, ahead of the candidate scan
 struct PatCol {
@@ -389,7 +389,7 @@ __device__ inline void swar_match_small(const uint8_t* Z, int Zn, const uint16_t
     const uint64_t m1 = L >= 16 ? ~0ull : L > 8 ? ((1ull << (8 * (L - 8))) - 1ull) : 0ull;
     hit = L > 0 && ((w0 ^ p0) & m0) == 0 && ((w1 ^ p1) & m1) == 0;
   }
-  // distinct tags never both match at one '<' (make_tagset): one writer per candidate
+  // distinct tags never both match at one '<' (make_tags): one writer per candidate
   if (hit) cand_tok[c] = (int8_t)(t < nts ? t + 1 : -(t - nts + 1));
 }
 
@@ -463,7 +463,7 @@ __device__ inline bool pattern_prefix_w(const uint8_t* Z, int q, int e, const KP
 // candidate's token — `lit` (the fast matcher's), or the class tag's when it comes first in the
 // tag list — or kClsSuspect.
 constexpr int kClsSuspect = 0x100;
-// Pair tag sets (TagClasses::nfold > 0: literal tags with a cased non-ASCII character) are of
+// Pair tag sets (is_pair_set: literal tags with a cased non-ASCII character) are of
 // the class kind for one reason: the text is folded as it is read, the upper member of a pair
 // standing for its lower member.  The fast matchers compare bytes, so they find every tag
 // written in lower case; a candidate they left is walked here with the fold — only when a byte
@@ -487,7 +487,7 @@ __device__ inline int fold_token(const uint8_t* Z, int Zn, int p, const KParams&
   return fold_match_dev(Z, Zn, p, &P.ts, P.cls);
 }
 __device__ __forceinline__ int class_token(const uint8_t* Z, int Zn, int p, const KParams& P, int lit) {
-  if (P.cls->nfold > 0) return lit != 0 ? lit : fold_token(Z, Zn, p, P);
+  if (is_pair_set(*P.cls)) return lit != 0 ? lit : fold_token(Z, Zn, p, P);
   int tok = 0, len = 0;
   const int r = class_candidate(Z, Zn, p, P.ts, *P.cls, false, &tok, &len);
   if (r == CC_SUSPECT) return kClsSuspect;
@@ -501,7 +501,7 @@ __device__ __forceinline__ int class_token(const uint8_t* Z, int Zn, int p, cons
 // Inside a block: a proper class-aware prefix of any pattern.  Bit 0: hold.
 __device__ __forceinline__ int class_hold(const uint8_t* Z, int q, int e, const KParams& P, int dq, int tk) {
   if (e - q > kMaxTail) return 0;
-  if (P.cls->nfold > 0) return fold_prefix_dev(Z, q, e, &P.ts, P.cls, dq == 0);  // (a pair tag set)
+  if (is_pair_set(*P.cls)) return fold_prefix_dev(Z, q, e, &P.ts, P.cls, dq == 0);
   if (dq == 0) {
     const bool pre = source_prefix(Z, q, e, P.ts, *P.cls);
     return (pre ? 1 : 0) | (tk > 0 && !pre ? 2 : 0);
@@ -2583,7 +2583,7 @@ enum : int { FV_CUR = 0, FV_PEND, FV_SEGA, FV_NSEG, FV_NTOK, FV_S0, FV_S1, FV_NB
 // when the candidate is suspect (qmx_text.h class_candidate).
 __device__ __forceinline__ int fin_class_token(const uint8_t* __restrict__ src, int n, int p, const TagSet& ts,
                                                const TagClasses& tc, int* L) {
-  if (tc.nfold > 0) {  // a pair tag set: the folded text's token
+  if (is_pair_set(tc)) {  // the folded text's token
     const int id = fold_match_dev(src, n, p, &ts, &tc);
     if (id != 0) *L = id > 0 ? ts.len[id - 1] + 2 : ts.len[-id - 1] + 3;
     return id;
@@ -2689,7 +2689,7 @@ __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n
               wave_fence();  // (FV_PPOS: lane 0's store at the open, maybe a window ago)
               const int ppos = F.v[FV_PPOS], cpos = __shfl(pos, L, 64), nl = ts.len[pend - 1];
               // (a pair tag set's tags are literal: open and close of one tag fold to the same bytes)
-              const bool ne = lane < nl && tc->nfold == 0 &&
+              const bool ne = lane < nl && !is_pair_set(*tc) &&
                               lower_ascii(src[ppos + 1 + lane]) != lower_ascii(src[cpos + 2 + lane]);
               if (__ballot(ne) != 0 && lane == 0) F.v[FV_CLS] = 1;
             }
@@ -3523,9 +3523,9 @@ void HipEngine::collect_timing(TickLane& L) {
   if (hipEventElapsedTime(&ms, L.ev0, L.ev1) == hipSuccess) L.kernel_ms += ms;
 }
 
-HipEngine::HipEngine(const std::vector<std::string>& tags, int device, int tile_bytes, int max_slots,
-                     int content_cap, int lanes, HipGrid* grid, int door, int ndoors, bool classes, bool unicode)
-    : HostEngine(tags, classes, unicode),
+HipEngine::HipEngine(const Tags& tags, int device, int tile_bytes, int max_slots, int content_cap, int lanes,
+                     HipGrid* grid, int door, int ndoors)
+    : HostEngine(tags),
       device_(device),
       tile_(std::min(std::max(tile_bytes, 1024), TILE_MAX) & ~15),
       max_slots_(max_slots),
@@ -3566,7 +3566,8 @@ HipEngine::HipEngine(const std::vector<std::string>& tags, int device, int tile_
   // a grid runs one kernel for all its doors: the literal tag sets' (qmx_tick_persistent) or
   // the one that carries the class paths and reads KParams::cls (qmx_ctick_persistent, a grid
   // made with `classes`) — the engine's tag set must be of the grid's kind
-  if (grid_ && (tag_classes(ts_) != nullptr) != grid_->classes()) {
+  const bool cls_kind = tags_.kind != TAGS_LITERAL;
+  if (grid_ && cls_kind != grid_->classes()) {
     if (!grid_->classes())
       throw std::invalid_argument("class thinking tags run on tick lanes (tick_mode lanes) or on a loop-tick grid "
                                   "made for them (HipGrid classes), not on a literal tag sets' grid");
@@ -3575,29 +3576,30 @@ HipEngine::HipEngine(const std::vector<std::string>& tags, int device, int tile_
   }
   // (tick lanes: a lane's own persistent grid is the literal kernel; a class tag set ticks
   // with a launch per tick there)
-  if (tag_classes(ts_) != nullptr) persistent_ = false;
+  if (cls_kind) persistent_ = false;
   HIP_CHECK(hipMalloc(&d_state_, sizeof(DevSlot) * (size_t)max_slots_));
   HIP_CHECK(hipMemset(d_state_, 0, sizeof(DevSlot) * (size_t)max_slots_));
   HIP_CHECK(hipMalloc(&d_content_, (size_t)content_cap_ * (size_t)max_slots_));
 
   std::memset(&base_params_, 0, sizeof(base_params_));
-  base_params_.ts = ts_;
-  if (const TagClasses* tc = tag_classes(ts_)) {
+  const TagSet& ts = tags_.ts;
+  base_params_.ts = ts;
+  if (cls_kind) {
     // class tags: the kernels read the class tables and the tags' source text from global
-    // memory, only where a class tag set needs them
+    // memory, only where a class tag set needs them (this engine's own copy)
     HIP_CHECK(hipMalloc((void**)&d_cls_, sizeof(TagClasses)));
-    HIP_CHECK(hipMemcpy(d_cls_, tc, sizeof(TagClasses), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_cls_, &tags_.tc, sizeof(TagClasses), hipMemcpyHostToDevice));
     base_params_.cls = d_cls_;
   }
-  base_params_.npat = 2 * ts_.n;
+  base_params_.npat = 2 * ts.n;
   // matcher codes: every byte that occurs in a pattern gets its own code (letters: one code
   // for both cases, the tags' IGNORECASE), everything else shares code 95
   {
     int next = 1;
     for (int b = 0; b < 256; ++b) base_params_.code[b] = 95;
     for (int p = 0; p < base_params_.npat; ++p)
-      for (int j = 0; j < pattern_len(ts_, p); ++j) {
-        const uint8_t b = pattern_byte(ts_, p, j);
+      for (int j = 0; j < pattern_len(ts, p); ++j) {
+        const uint8_t b = pattern_byte(ts, p, j);
         if (b >= 0x80 || base_params_.code[b] != 95) continue;  // (a class position is no byte; a non-ASCII tag's UTF-8 bytes have no case)
         if (next > 94) throw std::invalid_argument("thinking tags use more than 94 distinct characters");
         base_params_.code[b] = (uint8_t)next;
@@ -3610,17 +3612,17 @@ HipEngine::HipEngine(const std::vector<std::string>& tags, int device, int tile_
   auto digits = [](int b, int k) { return k == 0 ? (b & 7) : k == 1 ? ((b >> 3) & 7) : (b >> 6); };
   for (int p = 0; p < base_params_.npat; ++p) {
     int E = 0;
-    for (int j = 0; j < std::min(kWindow, pattern_len(ts_, p)); ++j) {
-      const int b = pattern_byte(ts_, p, j);
+    for (int j = 0; j < std::min(kWindow, pattern_len(ts, p)); ++j) {
+      const int b = pattern_byte(ts, p, j);
       for (int k = 0; k < 3; ++k) E += digits(b, k) * digits(b, k);
     }
     base_params_.pat_E[p] = E;
-    base_params_.plen[p] = pattern_len(ts_, p);
+    base_params_.plen[p] = pattern_len(ts, p);
   }
   base_params_.content_cap = content_cap_;
   for (int p = 0; p < base_params_.npat; ++p)
-    for (int j = 0; j < pattern_len(ts_, p); ++j)
-      base_params_.pw[p][j >> 3] |= (uint64_t)pattern_byte(ts_, p, j) << (8 * (j & 7));
+    for (int j = 0; j < pattern_len(ts, p); ++j)
+      base_params_.pw[p][j >> 3] |= (uint64_t)pattern_byte(ts, p, j) << (8 * (j & 7));
   base_params_.fast = 31;
   if (const char* kf = env_get("QMX_KFAST")) base_params_.fast = (uint32_t)strtoul(kf, nullptr, 0);
   for (int blk = 0; blk < 2; ++blk)
@@ -3628,8 +3630,8 @@ HipEngine::HipEngine(const std::vector<std::string>& tags, int device, int tile_
       const int t = 16 * blk + (l & 15), kg = l >> 4;
       for (int j = 0; j < 16; ++j) {
         int v = 0;
-        if (t < base_params_.npat && j < pattern_len(ts_, t)) {
-          const int b = pattern_byte(ts_, t, j);
+        if (t < base_params_.npat && j < pattern_len(ts, t)) {
+          const int b = pattern_byte(ts, t, j);
           v = kg < 3 ? -2 * digits(b, kg) : 1;  // -2·p digit, or the mask of the squares
         }
         base_params_.bfrag[blk][l * 16 + j] = (int8_t)v;
@@ -4075,7 +4077,7 @@ void HipEngine::prepare(HipJob& J) {
     if (slot >= max_slots_ || host_mode_[slot]) {
       bool was_closed = c.done || c.aborted;
       std::string o;
-      process_slot(ts_, c, (const uint8_t*)w.data.data(), w.data.size(), w.eof, J.created, o);
+      process_slot(tags_, c, (const uint8_t*)w.data.data(), w.data.size(), w.eof, J.created, o);
       int flags = (c.done ? RF_DONE : 0) | (c.aborted ? RF_ABORTED : 0) | RF_ESCALATED;
       if (!o.empty() || ((flags & (RF_DONE | RF_ABORTED)) && !was_closed))
         J.host_results.push_back({slot, std::move(o), flags});
@@ -4294,7 +4296,7 @@ void HipEngine::complete(HipJob& J, std::vector<SlotResult>& results, std::vecto
       all.swap(c.carry);
       bool was_closed = c.done || c.aborted;
       std::string o;
-      process_slot(ts_, c, (const uint8_t*)all.data(), all.size(), w.eof, J.created, o);
+      process_slot(tags_, c, (const uint8_t*)all.data(), all.size(), w.eof, J.created, o);
       int flags = (c.done ? RF_DONE : 0) | (c.aborted ? RF_ABORTED : 0) | RF_ESCALATED;
       if (!o.empty() || ((flags & (RF_DONE | RF_ABORTED)) && !was_closed)) results.push_back({p.slot, std::move(o), flags});
       return;
@@ -4561,7 +4563,7 @@ void HipEngine::finalize_host(const FinalizeReq& r, std::vector<FinalizeRes>& ou
   std::vector<std::string> texts;
   for (int s : r.slots) texts.push_back(text(s));
   FinalizeRes fr;
-  finalize_texts(ts_, texts, r, fr);
+  finalize_texts(tags_, texts, r, fr);
   out.push_back(std::move(fr));
   ++fin_host_;
 }

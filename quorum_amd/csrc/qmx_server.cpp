@@ -504,7 +504,7 @@ std::atomic<uint64_t> c_class_grid_launches{0}, c_class_grid_ticks{0};  // serve
 
 class Verifier {
  public:
-  Verifier(const std::vector<std::string>& tags, bool classes, bool unicode) : cpu_(tags, classes, unicode) {}
+  explicit Verifier(const Tags& tags) : cpu_(tags) {}
   void open(int slot, uint32_t gen, int index, bool f, bool e) {
     std::lock_guard<std::mutex> g(mu_);
     Track t;
@@ -683,11 +683,10 @@ static bool remote_hbm_direct(const ServerCfg& cfg) {
 class GpuHub {
  public:
   using Sink = std::function<void(ResultBatch&&)>;
-  GpuHub(const ServerCfg& cfg, int nloops) : cfg_(cfg), sinks_(nloops), pools_(nloops) {
+  GpuHub(const ServerCfg& cfg, int nloops, const Tags& tags) : cfg_(cfg), sinks_(nloops), pools_(nloops) {
     lanes_ = std::max(1, std::min(cfg.tick_lanes, 8));
     if (cfg.engine == "hip") {
-      HipEngine* he = new HipEngine(cfg.tags, cfg.device, cfg.tile, cfg.max_slots, cfg.content_cap, lanes_, nullptr, -1,
-                                     1, cfg.tag_classes, cfg.tag_unicode);
+      HipEngine* he = new HipEngine(tags, cfg.device, cfg.tile, cfg.max_slots, cfg.content_cap, lanes_);
       he->set_remote_hbm_direct(remote_hbm_direct(cfg));
       // (spread placement: an RCCL round writes a remote final text into the content arena
       // and its stream is synchronised before the text is applied; the finalize that reads it
@@ -695,8 +694,8 @@ class GpuHub {
       // persistent grids alike)
       eng_.reset(he);
     } else
-      eng_.reset(new CpuEngine(cfg.tags, cfg.tag_classes, cfg.tag_unicode));  // shared CPU engine: exercises the hub routing on CPU
-    if (cfg.verify) ver_.reset(new Verifier(cfg.tags, cfg.tag_classes, cfg.tag_unicode));
+      eng_.reset(new CpuEngine(tags));  // shared CPU engine: exercises the hub routing on CPU
+    if (cfg.verify) ver_.reset(new Verifier(tags));
   }
   ~GpuHub() {
     {
@@ -929,7 +928,8 @@ class GpuHub {
 // --------------------------------------------------------------------------------------
 class Loop {
  public:
-  Loop(const ServerCfg& cfg, int idx) : cfg_(cfg), idx_(idx) { xfd_ = eventfd(0, EFD_NONBLOCK); }
+  // (tags: the server's one tag set, run_server's)
+  Loop(const ServerCfg& cfg, int idx, const Tags& tags) : cfg_(cfg), idx_(idx), tags_(tags) { xfd_ = eventfd(0, EFD_NONBLOCK); }
   void attach_exchange(Exchange* x) { xch_ = x; }
   int index() const { return idx_; }
   void attach_hub(GpuHub* h) {
@@ -1259,8 +1259,8 @@ class Loop {
       if (grid_) {
         prctl(PR_SET_TIMERSLACK, 1000UL, 0, 0, 0);  // 1 us: the tick polls sleep a few us
         const int per = std::max(128, cfg_.max_slots / std::max(1, cfg_.threads));
-        heng_ = new HipEngine(cfg_.tags, cfg_.device, cfg_.tile, per, cfg_.content_cap, 1, grid_,
-                              idx_ * loop_doors_, loop_doors_, cfg_.tag_classes, cfg_.tag_unicode);
+        heng_ = new HipEngine(tags_, cfg_.device, cfg_.tile, per, cfg_.content_cap, 1, grid_, idx_ * loop_doors_,
+                              loop_doors_);
         heng_->set_remote_hbm_direct(remote_hbm_direct(cfg_));
         eng_.reset(heng_);
         aeng_ = heng_;
@@ -1268,12 +1268,12 @@ class Loop {
       } else if (cfg_.tick_mode == "loops") {
         // the loop-tick protocol on the CPU: jobs run on the engine's worker thread while the
         // loop polls for them (tests / TSan of the io loops' asynchronous tick path)
-        aeng_ = new AsyncCpuEngine(cfg_.tags, cfg_.tag_classes, cfg_.tag_unicode);
+        aeng_ = new AsyncCpuEngine(tags_);
         eng_.reset(aeng_);
       } else {
-        eng_.reset(new CpuEngine(cfg_.tags, cfg_.tag_classes, cfg_.tag_unicode));
+        eng_.reset(new CpuEngine(tags_));
       }
-      if (cfg_.verify) ver_.reset(new Verifier(cfg_.tags, cfg_.tag_classes, cfg_.tag_unicode));
+      if (cfg_.verify) ver_.reset(new Verifier(tags_));
     }
   }
 
@@ -3072,7 +3072,7 @@ class Loop {
         const JVal* msg = ch->a[0].get("message");
         const JVal* ct = msg ? msg->get("content") : nullptr;
         if (ct && cfg_.documented && cfg_.hide_aggregator_think && ct->t == JVal::STR)
-          return aggregate_result(s, JVal::str(strip_final(ts_, (const uint8_t*)ct->s.data(), ct->s.size())));
+          return aggregate_result(s, JVal::str(strip_final(tags_, (const uint8_t*)ct->s.data(), ct->s.size())));
         if (ct) return aggregate_result(s, *ct);
       }
     }
@@ -3223,7 +3223,7 @@ class Loop {
         err = strip ? "expected string or bytes-like object" : "sequence item 0: expected str instance";
         break;
       }
-      processed.push_back(strip ? strip_final(ts_, (const uint8_t*)content->s.data(),
+      processed.push_back(strip ? strip_final(tags_, (const uint8_t*)content->s.data(),
                                                         content->s.size())
                                           : content->s);
     }
@@ -3523,7 +3523,7 @@ class Loop {
     const char* e = env_get("QMX_LOOP_REQ_CHECK");
     return !e || atoi(e) != 0;
   }();
-  TagSet ts_ = make_tagset(cfg_.tags, cfg_.tag_classes, cfg_.tag_unicode);
+  const Tags& tags_;
   bool kick_ = false;
   std::mutex rmu_;
   std::vector<ResultBatch> rq_;
@@ -3701,9 +3701,11 @@ int run_server(const ServerCfg& cfg0) {
   g_stop.store(false);
   g_drain.store(false);
   g_ready.store(0);
+  // the one tag set of this server: every engine, the verify shadows and the loops share it
+  const Tags tags = make_tags(cfg.tags, cfg.tag_classes, cfg.tag_unicode);
   std::vector<std::unique_ptr<Loop>> loops;
   std::vector<std::thread> ts;
-  for (int i = 0; i < std::max(1, cfg.threads); ++i) loops.emplace_back(new Loop(cfg, i));
+  for (int i = 0; i < std::max(1, cfg.threads); ++i) loops.emplace_back(new Loop(cfg, i, tags));
   std::vector<Loop*> loop_ptrs;
   for (auto& l : loops) loop_ptrs.push_back(l.get());
   std::unique_ptr<GpuHub> hub;
@@ -3722,11 +3724,10 @@ int run_server(const ServerCfg& cfg0) {
   // is made with the flag and launches the kernel that carries the class paths
   // (qmx_ctick_persistent); the loops' engines carry the same tag set, so they pair with it.
   // (a pair tag set, runtime.native_unicode_tags, is of the class kind: its text is folded on read)
-  const bool cls_tags = (cfg.tag_classes || cfg.tag_unicode) &&
-                        tag_classes(make_tagset(cfg.tags, cfg.tag_classes, cfg.tag_unicode)) != nullptr;
+  const bool cls_tags = tags.kind != TAGS_LITERAL;
   const bool loop_ticks = hip && cfg.tick_mode != "lanes" && cfg.shared_engine != 1;
   const bool shared = !loop_ticks && (cfg.shared_engine < 0 ? hip : cfg.shared_engine > 0);
-  if (shared) hub.reset(new GpuHub(cfg, (int)loops.size()));
+  if (shared) hub.reset(new GpuHub(cfg, (int)loops.size(), tags));
   if (loop_ticks) {
     const char* w = env_get("QMX_GRID_WPD");
     const char* im = env_get("QMX_PERSISTENT_IDLE_MS");
@@ -3741,7 +3742,7 @@ int run_server(const ServerCfg& cfg0) {
                              im ? atoi(im) : 50, cls_tags));
     } catch (const std::exception& e) {  // e.g. more io loops than a partitioned GPU has CUs
       fprintf(stderr, "qmx: loop ticks unavailable (%s) — tick lanes instead\n", e.what());
-      hub.reset(new GpuHub(cfg, (int)loops.size()));
+      hub.reset(new GpuHub(cfg, (int)loops.size(), tags));
     }
   }
   for (auto& l : loops) {

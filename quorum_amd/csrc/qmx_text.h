@@ -34,7 +34,13 @@ constexpr int kJsonMaxDepth = 256;  // deeper == RecursionError (stream abort)
 // ---------------------------------------------------------------------------
 // tag patterns
 // ---------------------------------------------------------------------------
-// Class tags (make_tagset(tags, classes = true)): the fixed-width part of the regex language
+// The three kinds of tag set (host code keeps the kind with the tables: Tags, qmx_engine.h).
+//   literal: ASCII or uncased tags, compared byte for byte (ASCII letters lowercased);
+//   class:   some tag took the class parser (a class element or an escape);
+//   pair:    literal tags with a cased non-ASCII character, the text folded as it is read.
+enum TagKind : int { TAGS_LITERAL, TAGS_CLASS, TAGS_PAIR };
+
+// Class tags (make_tags(tags, classes = true)): the fixed-width part of the regex language
 // the reference's alternation speaks — '.', bracket classes and escaped punctuation.  A tag is
 // then a sequence of elements that match one code point each; name[] keeps a literal element
 // as its lowercase byte and a class element as 0x80 + its index into TagClasses (pattern bytes
@@ -48,7 +54,7 @@ struct TagClasses {
   uint8_t flags[kMaxClasses];
   int srclen[kMaxTags];
   uint8_t src[kMaxTags][kMaxTagLen + 1];  // the tag's lowercased source text (depth-0 holdback)
-  // Pair tag sets (make_tagset(tags, classes, unicode = true), a non-ASCII cased character in
+  // Pair tag sets (make_tags(tags, classes, unicode = true), a non-ASCII cased character in
   // a tag): the tags are literal — n == 0, name[] holds the UTF-8 bytes of the lowercased tag —
   // and the text is folded as it is read: the upper member of a pair stands for its lower
   // member (same byte length).  A character's bytes are packed little-endian, byte k at bit 8k.
@@ -57,19 +63,18 @@ struct TagClasses {
   uint8_t fold_len[kMaxFold];
   uint32_t fold_up[kMaxFold], fold_lo[kMaxFold];
 };
+// The kernels of the class kind run class and pair tag sets (KParams::cls is set for both):
+// which of the two the tables are.
+QMX_HD bool is_pair_set(const TagClasses& tc) { return tc.nfold > 0; }
 
-// (The layout of TagSet is the literal tag sets': the kernels keep a copy in LDS.  A class
-// tag set is marked in the one spare byte of name[0] — a tag is at most kMaxTagLen bytes —
-// with the id of its TagClasses: host code finds them with tag_classes(), qmx_engine.h, the
-// kernels get a pointer to their device copy in KParams.)
+// (The layout of TagSet is the literal tag sets': the kernels keep a copy in LDS.  The tables
+// of a class or pair tag set travel beside it: Tags::tc on the host, a device copy behind
+// KParams::cls in the kernels.)
 struct TagSet {
   int n;                                   // distinct lowercase tags
   int len[kMaxTags];
   uint8_t name[kMaxTags][kMaxTagLen + 1];  // lowercase ASCII (class tags: see TagClasses)
 };
-// 0: a literal tag set; else some tag has a class element or an escape, or (a pair tag set)
-// a non-ASCII cased character
-QMX_HD int tagset_cls_id(const TagSet& ts) { return ts.name[0][kMaxTagLen]; }
 
 QMX_HD uint8_t lower_ascii(uint8_t c) { return (c >= 'A' && c <= 'Z') ? (uint8_t)(c + 32) : c; }
 
@@ -123,7 +128,7 @@ QMX_HD bool pattern_prefix(const R& x, int q, int n, const TagSet& ts, bool open
 }
 
 // ---------------------------------------------------------------------------
-// class tags: one code point per element (tagset_cls_id(ts) != 0; tc: the set's TagClasses)
+// class tags: one code point per element (TAGS_CLASS; tc: the set's TagClasses)
 // ---------------------------------------------------------------------------
 // Does class element `k` accept the ASCII byte c?  The streaming filter's regex has no DOTALL
 // (a dot rejects '\n' there); the final strip's has.
@@ -258,7 +263,7 @@ QMX_HD bool source_prefix(const R& x, int q, int n, const TagSet& ts, const TagC
 }
 
 // ---------------------------------------------------------------------------
-// pair tags: literal patterns, the text folded on read (tc.nfold > 0)
+// pair tags: literal patterns, the text folded on read (TAGS_PAIR)
 // ---------------------------------------------------------------------------
 // Walk pattern `pat` over x[p:n), every character of the text as the patterns see it: an ASCII
 // letter lowercased, the upper member of a pair replaced by its lower member.  Both have the
@@ -319,6 +324,26 @@ QMX_HD bool fold_pattern_prefix(const R& x, int q, int n, const TagSet& ts, cons
     if (fold_walk(x, n, q, ts, tc, pat) != 0) return true;
   }
   return false;
+}
+
+// ---------------------------------------------------------------------------
+// the three families behind one kind
+// ---------------------------------------------------------------------------
+// Token at position p of x[0:n), as match_at (strip: a class tag set's final-strip tables).
+template <class R>
+QMX_HD int token_at(TagKind kind, const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, bool strip,
+                    int* tok_len) {
+  return kind == TAGS_CLASS ? class_match_at(x, n, p, ts, tc, strip, tok_len)
+       : kind == TAGS_PAIR  ? fold_match_at(x, n, p, ts, tc, tok_len)
+                            : match_at(x, n, p, ts, tok_len);
+}
+
+// Is x[q:n), the text from the last '<', held back at depth `depth`?  A class tag set holds the
+// tags' source text outside a block and a proper prefix of a pattern inside one.
+template <class R>
+QMX_HD bool held_at(TagKind kind, const R& x, int q, int n, const TagSet& ts, const TagClasses& tc, int depth) {
+  if (kind == TAGS_CLASS) return depth == 0 ? source_prefix(x, q, n, ts, tc) : class_prefix(x, q, n, ts, tc);
+  return kind == TAGS_PAIR ? fold_pattern_prefix(x, q, n, ts, tc, depth == 0) : pattern_prefix(x, q, n, ts, depth == 0);
 }
 
 // ---------------------------------------------------------------------------

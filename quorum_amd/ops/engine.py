@@ -76,7 +76,7 @@ def native_tag_ok(tags: Sequence[str], max_tags: int = 16, max_len: int = 61, cl
     Anything else runs on the python engine with real regex semantics.
 
     ``classes`` (``runtime.native_regex_tags``): also the class tags — '.', bracket classes
-    and escaped punctuation after a literal first element.  The C++ parser (``make_tagset``)
+    and escaped punctuation after a literal first element.  The C++ parser (``make_tags``)
     is the one definition of that subset, so it is asked.
 
     ``unicode`` (``runtime.native_unicode_tags``): also non-ASCII tags whose characters are
@@ -216,11 +216,9 @@ def make_engine(kind: str, tags: Sequence[str], device: Optional[int] = None, **
             logger.warning("native extension not built: using the python engine")
             return _py_engine(tags)
         kind = "hip" if native.gpu_available() else "cpu"
-    # (class tags keep their case in the key: "[Z-a]" and "[z-a]" are different patterns)
-    # (so do tags that may be non-ASCII: the C++ parser lowercases them through its pair table)
-    asis = classes or unicode
-    key = ((kind, classes, unicode) if asis else kind, tuple(t if asis else t.lower() for t in tags),
-           -1 if device is None else device)
+    # (the tags as they reach the extension: "[Z-a]" and "[z-a]" are different patterns)
+    key = ((kind, classes, unicode) if classes or unicode else kind,
+           tuple(native.sent_tags(tags, classes, unicode)), -1 if device is None else device)
     eng = _NATIVE_CACHE.get(key)
     if eng is None:
         if unicode:

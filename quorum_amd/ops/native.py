@@ -51,14 +51,17 @@ def gpu_available() -> bool:
         return False
 
 
+def sent_tags(tags: Sequence[str], classes: bool = False, unicode: bool = False) -> List[str]:
+    """The tag list as it is sent to the extension, first occurrence only.  Class and non-ASCII
+    tags go down as written (lowercasing would turn "[Z-a]" into another pattern; the C++ parser
+    folds non-ASCII tags through its pair table), plain tags through ``str.lower()``, which is
+    more than ASCII lowercasing: "THIN\u212a" (Kelvin sign) is "think" and runs; as written it would not."""
+    return list(dict.fromkeys(t if classes or unicode else t.lower() for t in tags))
+
+
 def strip_fn(tags: Sequence[str], classes: bool = False, unicode: bool = False) -> Callable[[str, bool], str]:
     ext = require()
-    # class tags go down as written: lowercasing would turn "[Z-a]" into another pattern (and
-    # non-ASCII tags are lowercased by the C++ parser, through its pair table)
-    if classes or unicode:
-        stripper = ext.Stripper(list(tags), classes=bool(classes), unicode=bool(unicode))
-    else:
-        stripper = ext.Stripper([t.lower() for t in tags])
+    stripper = ext.Stripper(sent_tags(tags, classes, unicode), classes=bool(classes), unicode=bool(unicode))
 
     def _strip(text, on):
         if not on:
@@ -93,13 +96,7 @@ class NativeEngine:
         self.tags: List[str] = list(tags)
         self.classes = bool(classes)
         self.unicode = bool(unicode)
-        low = []
-        for t in tags:
-            # class tags go down as written: lowercasing would turn "[Z-a]" into another pattern
-            # (non-ASCII tags too: the C++ parser lowercases them through its pair table)
-            t = t if classes or unicode else t.lower()
-            if t not in low:
-                low.append(t)
+        low = sent_tags(tags, classes, unicode)
         if kind == "hip":
             if ext.device_count() <= 0:
                 raise RuntimeError("engine 'hip' requested but no GPU is visible")

@@ -5,9 +5,9 @@
 //  * streaming invariance: the C++ CPU engine produces byte-identical SSE output, flags,
 //    content and finals whether a stream is fed in one piece or split at random points with
 //    ticks at random moments (the tile/carry/holdback logic of every split point) — with the
-//    default tags and with class tag sets ('.', "[...]", escapes: make_tagset(tags, true)),
+//    default tags and with class tag sets ('.', "[...]", escapes: make_tags(tags, true)),
 //    their pieces including multi-byte code points and '<' / '>' at class positions, and with
-//    non-ASCII tag sets (make_tagset(tags, false, true): uncased and case-pair characters, the
+//    non-ASCII tag sets (make_tags(tags, false, true): uncased and case-pair characters, the
 //    text folded on read), their pieces in both cases, look-alikes and JSON-escaped forms;
 //  * strip_final idempotence on already-stripped text and JSON DOM round-trips
 //    (parse(dump(parse(x))) == parse(x)), py_float_repr/escape on random inputs;
@@ -39,7 +39,7 @@ const char* kPieces[] = {"<think>", "</think>", "<THINK>", "</Think>", "<reason>
 struct ClassSet {
   std::vector<std::string> tags;
   std::vector<const char*> pieces;
-  bool unicode = false;  // a non-ASCII tag set (make_tagset's `unicode`), no class tags
+  bool unicode = false;  // a non-ASCII tag set (make_tags' `unicode`), no class tags
 };
 const ClassSet kClassSets[] = {
     {{"think", "th.nk"},
@@ -99,9 +99,8 @@ struct Run {
   std::vector<std::string> fin_texts;
 };
 
-Run run_engine(const std::vector<std::string>& tags, const std::vector<std::string>& bodies,
-               const std::vector<bool>& filt, bool split) {
-  CpuEngine eng(tags, g_class != nullptr && !g_class->unicode, g_class != nullptr && g_class->unicode);
+Run run_engine(const Tags& tags, const std::vector<std::string>& bodies, const std::vector<bool>& filt, bool split) {
+  CpuEngine eng(tags);
   Run out;
   std::vector<int> slots;
   for (size_t i = 0; i < bodies.size(); ++i) slots.push_back(eng.open((int)i, filt[i], true));
@@ -197,7 +196,8 @@ int main(int argc, char** argv) {
   for (int it = 0; it < iters; ++it) {
     // every other iteration: one of the class tag sets
     g_class = it % 2 ? &kClassSets[(it / 2) % (int)(sizeof(kClassSets) / sizeof(kClassSets[0]))] : nullptr;
-    const std::vector<std::string>& tags = g_class ? g_class->tags : default_tags;
+    const Tags tags = make_tags(g_class ? g_class->tags : default_tags, g_class != nullptr && !g_class->unicode,
+                                g_class != nullptr && g_class->unicode);
     int ns = 1 + R(4);
     std::vector<std::string> bodies;
     std::vector<bool> filt;
@@ -215,10 +215,9 @@ int main(int argc, char** argv) {
       if (++fails <= 3) fprintf(stderr, "streaming invariance violated (iteration %d)\n", it);
     }
     // strip_final: stripping a stripped text (no tags left in it) only re-strips whitespace
-    TagSet ts = make_tagset(tags, g_class != nullptr && !g_class->unicode, g_class != nullptr && g_class->unicode);
     std::string t = rand_content() + rand_content();
-    std::string s1 = strip_final(ts, (const uint8_t*)t.data(), t.size());
-    std::string s2 = strip_final(ts, (const uint8_t*)s1.data(), s1.size());
+    std::string s1 = strip_final(tags, (const uint8_t*)t.data(), t.size());
+    std::string s2 = strip_final(tags, (const uint8_t*)s1.data(), s1.size());
     (void)s2;
     // JSON DOM round trip
     std::string js = rand_json();

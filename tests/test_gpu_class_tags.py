@@ -267,6 +267,25 @@ def test_finalize_close_must_equal_the_captured_text():
 
 
 # ---------------------------------------------------------------- plumbing
+def test_two_engines_keep_their_own_tables():
+    """Two one-shot engines with different class tag sets in one process, both made before
+    either runs: one slot and one content event each, finished and finalized with strip on —
+    deltas, flags, content and the final event equal to a CPU engine of the same tags (an
+    engine reading the other's device tables would strip the other's block)."""
+    text = "<thXnk>a</thXnk>b<th1nk>c</th1nk>d"
+    sets = [["th.nk"], ["th[0-9]nk"]]
+    hips = [_hip(t) for t in sets]
+    rng = random.Random(9)
+    streams = [[H.event_bytes(rng, text) + b"data: [DONE]\n\n"]]
+    for tags, hip, content in zip(sets, hips, ["bd", "<thXnk>a</thXnk>bd"]):
+        want = H.run_engine(_cpu(tags), streams, [True], [True], H.EveryRound())
+        got = H.run_engine(hip, streams, [True], [True], H.EveryRound())
+        assert got == want, tags
+        assert got[0][0][1:] == (1, content) and got[2] == [content], (tags, got)
+        st = _stats(hip)
+        assert st["escalations"] == 0 and st["fin_host"] == 0 and st["fin_items"] >= 1, st
+
+
 def test_class_tags_need_tick_lanes():
     """The loop-tick grid runs the literal tag sets' kernel: an engine with a class tag set on a
     door of it is refused (the server picks tick lanes for such a config); a literal tag set
