@@ -25,7 +25,8 @@ namespace {
 struct PyStreamFilter {
   Tags tags;
   FilterState fs;
-  PyStreamFilter(const std::vector<std::string>& t, bool classes, bool unicode) : tags(make_tags(t, classes, unicode)) {}
+  PyStreamFilter(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed)
+      : tags(make_tags(t, classes, unicode, mixed)) {}
   py::bytes feed(const std::string& s) {
     std::string out;
     filter_feed(tags, fs, (const uint8_t*)s.data(), s.size(), out);
@@ -39,7 +40,8 @@ struct PyStreamFilter {
 
 struct PyStripper {
   Tags tags;
-  PyStripper(const std::vector<std::string>& t, bool classes, bool unicode) : tags(make_tags(t, classes, unicode)) {}
+  PyStripper(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed)
+      : tags(make_tags(t, classes, unicode, mixed)) {}
   py::bytes strip(const std::string& s) { return py::bytes(strip_final(tags, (const uint8_t*)s.data(), s.size())); }
 };
 
@@ -139,6 +141,7 @@ ServerCfg server_cfg_from(const py::dict& d) {
   if (d.contains("tags")) c.tags = py::cast<std::vector<std::string>>(d["tags"]);
   gb("tag_classes", c.tag_classes);
   gb("tag_unicode", c.tag_unicode);
+  gb("tag_mixed", c.tag_mixed);
   gs("aggregator_name", c.aggregator_name); gs("prompt_template", c.prompt_template);
   gs("intermediate_separator", c.intermediate_separator); gs("query_format", c.query_format);
   gs("source_label_format", c.source_label_format); gb("include_original_query", c.include_original_query);
@@ -476,36 +479,39 @@ PYBIND11_MODULE(_qmx, m) {
     return py::bytes(out);
   });
   py::class_<PyStreamFilter>(m, "StreamFilter")
-      .def(py::init<const std::vector<std::string>&, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
-           py::arg("unicode") = false)
+      .def(py::init<const std::vector<std::string>&, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
+           py::arg("unicode") = false, py::arg("mixed") = false)
       .def("feed", &PyStreamFilter::feed)
       .def("flush", &PyStreamFilter::flush);
   py::class_<PyStripper>(m, "Stripper")
-      .def(py::init<const std::vector<std::string>&, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
-           py::arg("unicode") = false)
+      .def(py::init<const std::vector<std::string>&, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
+           py::arg("unicode") = false, py::arg("mixed") = false)
       .def("strip", &PyStripper::strip);
   // is this tag list inside what make_tags runs natively (the one definition of the subset)?
-  m.def("tagset_ok", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
+  m.def("tagset_ok", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed) {
     try {
-      make_tags(tags, classes, unicode);
+      make_tags(tags, classes, unicode, mixed);
       return true;
     } catch (const std::invalid_argument&) {
       return false;
     }
-  }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
+  }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
+     py::arg("mixed") = false);
   // why make_tags refuses this tag list ("" when it does not): the limit's own message
-  m.def("tagset_error", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
+  m.def("tagset_error", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed) {
     try {
-      make_tags(tags, classes, unicode);
+      make_tags(tags, classes, unicode, mixed);
       return std::string();
     } catch (const std::invalid_argument& e) {
       return std::string(e.what());
     }
-  }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
+  }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
+     py::arg("mixed") = false);
   // distinct tags of the set make_tags builds ("É" and "é" are one)
-  m.def("tagset_size", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
-    return make_tags(tags, classes, unicode).ts.n;
-  }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
+  m.def("tagset_size", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed) {
+    return make_tags(tags, classes, unicode, mixed).ts.n;
+  }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
+     py::arg("mixed") = false);
   // the case rule of one non-ASCII tag character (qmx_unicode_fold.h): (kind, partner) with
   // kind 0 uncased, 1 a simple case pair, 2 refused; partner: the pair's other member, else cp
   m.def("unicode_tag_char", [](uint32_t cp) {
@@ -514,34 +520,41 @@ PYBIND11_MODULE(_qmx, m) {
     return py::make_tuple(kind, kind == 1 ? unicode_tag_partner(cp) : cp);
   });
   // the kind of the tag set this list makes (qmx_text.h TagKind)
-  m.def("tagset_kind", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
-    const TagKind k = make_tags(tags, classes, unicode).kind;
-    return k == TAGS_PAIR ? "pair" : k == TAGS_CLASS ? "class" : "literal";
-  }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
-  // of the class kind (class or pair)?  Such a tag set's engines need HipGrid(classes=True)
-  m.def("tagset_has_classes", [](const std::vector<std::string>& tags, bool classes, bool unicode) {
-    return make_tags(tags, classes, unicode).kind != TAGS_LITERAL;
-  }, py::arg("tags"), py::arg("classes") = true, py::arg("unicode") = false);
+  m.def("tagset_kind", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed) {
+    const TagKind k = make_tags(tags, classes, unicode, mixed).kind;
+    return k == TAGS_MIXED ? "mixed" : k == TAGS_PAIR ? "pair" : k == TAGS_CLASS ? "class" : "literal";
+  }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
+     py::arg("mixed") = false);
+  // of the class kind (class, pair or mixed)?  Such a tag set's engines need HipGrid(classes=True)
+  m.def("tagset_has_classes", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed) {
+    return make_tags(tags, classes, unicode, mixed).kind != TAGS_LITERAL;
+  }, py::arg("tags"), py::arg("classes") = true, py::arg("unicode") = false,
+     py::arg("mixed") = false);
   // candidates '<' of `text` the GPU kernels would hand to the host path (qmx_text.h
   // class_candidate, the shared suspect rule), with the streaming or the strip tables
-  m.def("class_suspects", [](const std::vector<std::string>& tags, const std::string& text, bool strip) {
-    const Tags t = make_tags(tags, true);
+  m.def("class_suspects", [](const std::vector<std::string>& tags, const std::string& text, bool strip, bool unicode,
+                             bool mixed) {
+    const Tags t = make_tags(tags, true, unicode, mixed);
     int k = 0;
     if (t.kind == TAGS_LITERAL) return k;
     const uint8_t* x = (const uint8_t*)text.data();
     for (int p = 0; p < (int)text.size(); ++p) {
       int tok = 0, len = 0;
-      if (x[p] == '<' && class_candidate(x, (int)text.size(), p, t.ts, t.tc, strip, &tok, &len) == CC_SUSPECT) ++k;
+      if (x[p] != '<' || t.kind == TAGS_PAIR) continue;  // (a pair tag set has no suspect candidate)
+      const int r = t.kind == TAGS_MIXED ? mixed_candidate(x, (int)text.size(), p, t.ts, t.tc, strip, &tok, &len)
+                                         : class_candidate(x, (int)text.size(), p, t.ts, t.tc, strip, &tok, &len);
+      if (r == CC_SUSPECT) ++k;
     }
     return k;
-  }, py::arg("tags"), py::arg("text"), py::arg("strip") = false);
+  }, py::arg("tags"), py::arg("text"), py::arg("strip") = false, py::arg("unicode") = false, py::arg("mixed") = false);
   env_refresh();
   py::class_<CpuEngine> ce(m, "CpuEngine");
-  ce.def(py::init([](const std::vector<std::string>& tags, bool classes, bool unicode) {
+  ce.def(py::init([](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed) {
            env_refresh();
-           return new CpuEngine(make_tags(tags, classes, unicode));
+           return new CpuEngine(make_tags(tags, classes, unicode, mixed));
          }),
-         py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false);
+         py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
+     py::arg("mixed") = false);
   bind_engine(ce);
   // the multi-door grid of loop ticks (tests drive several door engines from Python threads)
   py::class_<HipGrid>(m, "HipGrid")
@@ -586,14 +599,15 @@ PYBIND11_MODULE(_qmx, m) {
         py::call_guard<py::gil_scoped_release>());
   py::class_<HipEngine> he(m, "HipEngine");
   he.def(py::init([](const std::vector<std::string>& tags, int device, int tile, int max_slots, int content_cap,
-                      int lanes, HipGrid* grid, int door, int ndoors, bool classes, bool unicode) {
+                      int lanes, HipGrid* grid, int door, int ndoors, bool classes, bool unicode, bool mixed) {
            env_refresh();
-           return new HipEngine(make_tags(tags, classes, unicode), device, tile, max_slots, content_cap, lanes, grid,
+           return new HipEngine(make_tags(tags, classes, unicode, mixed), device, tile, max_slots, content_cap, lanes, grid,
                                 door, ndoors);
          }),
          py::arg("tags"), py::arg("device"), py::arg("tile_bytes") = 16384, py::arg("max_slots") = 8192,
          py::arg("content_cap") = 1 << 20, py::arg("lanes") = 1, py::arg("grid") = nullptr, py::arg("door") = -1,
-         py::arg("ndoors") = 1, py::arg("classes") = false, py::arg("unicode") = false, py::keep_alive<1, 8>());
+         py::arg("ndoors") = 1, py::arg("classes") = false, py::arg("unicode") = false, py::arg("mixed") = false,
+         py::keep_alive<1, 8>());
   bind_engine(he);
   he.def("kernel_stats", &HipEngine::kernel_stats);
   he.def("debug_poison_results", &HipEngine::debug_poison_results, py::arg("ahead") = 1);

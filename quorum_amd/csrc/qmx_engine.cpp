@@ -87,8 +87,10 @@ bool parse_bracket(const std::string& t, size_t& i, Elem& e) {
   return true;
 }
 
-// The elements of one tag, or false when it lies outside the class subset.
-bool parse_class_tag(const std::string& t, std::vector<Elem>& out) {
+// The elements of one tag, or false when it lies outside the class subset.  wide: a byte
+// >= 0x80 outside a bracket class is a literal element of its own (a mixed tag set: the bytes of
+// a non-ASCII literal character, already lowered through the pair table).
+bool parse_class_tag(const std::string& t, std::vector<Elem>& out, bool wide = false) {
   for (size_t i = 0; i < t.size();) {
     const uint8_t c = (uint8_t)t[i];
     Elem e;
@@ -103,6 +105,9 @@ bool parse_class_tag(const std::string& t, std::vector<Elem>& out) {
       ++i;
     } else if (c == '[') {
       if (!parse_bracket(t, i, e)) return false;
+    } else if (wide && c >= 0x80) {
+      e.lit = c;
+      ++i;
     } else {
       if (!printable(c) || std::strchr("^$*+?{}]|()<>/", (int)c)) return false;
       e.lit = lower_ascii(c);
@@ -141,12 +146,14 @@ uint32_t unicode_tag_partner(uint32_t cp) {
   return cp;
 }
 
-Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode) {
+Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed) {
+  mixed = mixed && classes && unicode;
   Tags out;
   std::memset(&out, 0, sizeof(out));
   TagSet& ts = out.ts;
   TagClasses& tc = out.tc;
   bool any_cls = false, any_wide = false;
+  uint32_t pair_tags = 0;  // bit t: tag t holds a pair character
   std::vector<std::string> seen;
   auto pack = [](uint32_t cp, int* len) {  // UTF-8 bytes, byte k at bit 8k
     uint8_t b[4];
@@ -156,8 +163,8 @@ Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode)
     return v;
   };
   for (const auto& t0 : tags) {
-    std::string t;
-    bool wide = false;
+    std::string t, tw;  // tw: the tag as written, its non-ASCII characters lowered (mixed: the class parser's input)
+    bool wide = false, has_pair = false;
     for (char c : t0) wide = wide || (uint8_t)c >= 0x80;
     if (wide && unicode) {
       // a non-ASCII tag: its characters are uncased or one of a simple case pair, lowercased
@@ -170,6 +177,7 @@ Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode)
         p += wtf8_decode(b, p, n, &cp);
         if (cp < 0x80) {
           t.push_back((char)lower_ascii((uint8_t)cp));
+          tw.push_back((char)cp);
           continue;
         }
         const int kind = unicode_tag_char(cp, &low);
@@ -177,6 +185,8 @@ Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode)
           throw std::invalid_argument("tag holds a character without a simple case pair (runs with --impl python): " + t0);
         uint8_t o[4];
         t.append((const char*)o, (size_t)put_wtf8(low, o));
+        tw.append((const char*)o, (size_t)put_wtf8(low, o));
+        has_pair = has_pair || kind == 1;
         if (kind == 1) {
           int ln;
           const uint32_t lo = pack(low, &ln), up = pack(unicode_tag_partner(low), &ln);
@@ -213,14 +223,16 @@ Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode)
     if (!literal) {
       // class tags: '.', [...] and escaped punctuation, one code point per element; the
       // tables come from the tag as written (IGNORECASE makes its case immaterial)
-      if (!classes || !parse_class_tag(t0, elems)) throw std::invalid_argument("tag needs regex semantics: " + t0);
+      const bool mix = mixed && wide;  // a class element and a non-ASCII literal in one tag
+      if (!classes || !parse_class_tag(mix ? tw : t0, elems, mix)) throw std::invalid_argument("tag needs regex semantics: " + t0);
       int bound = 3;  // bytes of the longest "</" + match + ">"
       for (const Elem& e : elems) bound += (e.flags & CLS_WIDE) ? 4 : 1;
       if (bound > kMaxTail) throw std::invalid_argument("unsupported tag length: " + t0);
     }
     if (ts.n >= kMaxTags) throw std::invalid_argument("too many thinking tags");
     seen.push_back(t);
-    any_wide = any_wide || (literal && wide);
+    any_wide = any_wide || wide;  // (a bracket class has ASCII members: every byte >= 0x80 is a literal's)
+    if (has_pair) pair_tags |= 1u << ts.n;
     tc.srclen[ts.n] = (int)t.size();
     std::memcpy(tc.src[ts.n], t.data(), t.size());
     if (literal) {
@@ -235,6 +247,7 @@ Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode)
           ts.name[ts.n][i] = e.lit;
           continue;
         }
+        tc.clsmask[ts.n] |= 1ull << i;
         int k = 0;
         while (k < tc.n && !(tc.flags[k] == e.flags && std::memcmp(tc.tab[k], e.tab, sizeof(e.tab)) == 0)) ++k;
         if (k == tc.n) {
@@ -250,12 +263,21 @@ Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode)
   }
   if (ts.n == 0) throw std::invalid_argument("empty tag set");
   // a class position is kept as byte 0x80 + k in TagSet::name, where a non-ASCII tag keeps
-  // its UTF-8 bytes
-  if (any_cls && any_wide)
+  // its UTF-8 bytes: only a mixed tag set (`mixed`) tells the two apart, by TagClasses::clsmask
+  if (any_cls && any_wide && !mixed)
     throw std::invalid_argument("class tags and non-ASCII tags do not mix in one tag set (runs with --impl python)");
   if (tc.nfold > 0)
     for (int pat = 0; pat < 2 * ts.n; ++pat) tc.span = std::max(tc.span, pattern_len(ts, pat));
-  out.kind = tc.nfold > 0 ? TAGS_PAIR : any_cls ? TAGS_CLASS : TAGS_LITERAL;
+  out.kind = any_cls && any_wide ? TAGS_MIXED : tc.nfold > 0 ? TAGS_PAIR : any_cls ? TAGS_CLASS : TAGS_LITERAL;
+  if (out.kind == TAGS_MIXED) {
+    tc.nfold = -(tc.nfold + 1);  // (mixed_nfold: the kernels tell the three kinds apart by this one word)
+    tc.walk = pair_tags;
+    for (int t = 0; t < ts.n; ++t)
+      if (tc.clsmask[t]) tc.walk |= 1u << t;
+  } else {
+    std::memset(tc.clsmask, 0, sizeof(tc.clsmask));  // (the tables of the other kinds are what they were)
+    tc.walk = 0;
+  }
   // (a literal tag set keeps no tables: its source text is its names)
   if (out.kind == TAGS_LITERAL) std::memset(&tc, 0, sizeof(tc));
   return out;
@@ -297,7 +319,7 @@ void filter_feed(const Tags& tags, FilterState& fs, const uint8_t* text, size_t 
     // no more tokens: hold back a trailing partial tag from the LAST '<'
     int q = N - 1;
     bool hold;
-    if (tags.kind == TAGS_CLASS && fs.depth > 0) {
+    if ((tags.kind == TAGS_CLASS || tags.kind == TAGS_MIXED) && fs.depth > 0) {
       // class tags inside a block: a class element may swallow a later '<', so keep from the
       // EARLIEST '<' whose rest is still a proper prefix of some pattern (the reference keeps
       // its whole buffer here; the byte bound of make_tags keeps this within kMaxTail)
@@ -327,10 +349,31 @@ void filter_feed(const Tags& tags, FilterState& fs, const uint8_t* text, size_t 
 // an alternative without a close gives way to the next one.  The closes are indexed once by
 // (tag, folded capture) — a text equal to a capture of tag t matches t's elements too — so the
 // walk stays near linear where the regex is quadratic.
-static std::string strip_final_classes(const TagSet& ts, const TagClasses& tc, const uint8_t* x, int n) {
+// A mixed tag set: the same walk over mixed_walk, the capture keys folded through the pair table
+// as well (the upper member of one of the set's pair characters stands for its lower member).
+static std::string strip_final_classes(const Tags& tags, const uint8_t* x, int n) {
+  const TagSet& ts = tags.ts;
+  const TagClasses& tc = tags.tc;
+  const bool mixed = tags.kind == TAGS_MIXED;
+  auto walk = [&](int p, int pat, int* end) {
+    return mixed ? mixed_walk(x, n, p, ts, tc, pat, true, end) : class_walk(x, n, p, ts, tc, pat, true, end);
+  };
   auto key_of = [&](int t, int a, int b) {
     std::string k(1, (char)t);
-    for (int i = a; i < b; ++i) k.push_back((char)lower_ascii(x[i]));
+    for (int i = a; i < b;) {
+      const int ln = mixed ? utf8_lead_len(x[i]) : 1;
+      if (ln > 1 && i + ln <= b) {
+        uint32_t have = 0;
+        for (int j = 0; j < ln; ++j) have |= (uint32_t)x[i + j] << (8 * j);
+        for (int f = 0; f < mixed_nfold(tc); ++f)
+          if (tc.fold_len[f] == ln && tc.fold_up[f] == have) have = tc.fold_lo[f];
+        for (int j = 0; j < ln; ++j) k.push_back((char)(have >> (8 * j)));
+        i += ln;
+        continue;
+      }
+      k.push_back((char)lower_ascii(x[i]));
+      ++i;
+    }
     return k;
   };
   std::unordered_map<std::string, std::vector<int>> closes;  // -> positions of the "</", ascending
@@ -338,7 +381,7 @@ static std::string strip_final_classes(const TagSet& ts, const TagClasses& tc, c
     if (x[p] != '<' || x[p + 1] != '/') continue;
     for (int t = 0; t < ts.n; ++t) {
       int end = 0;
-      if (class_walk(x, n, p, ts, tc, ts.n + t, true, &end) == 1) closes[key_of(t, p + 2, end - 1)].push_back(p);
+      if (walk(p, ts.n + t, &end) == 1) closes[key_of(t, p + 2, end - 1)].push_back(p);
     }
   }
   std::string out;
@@ -348,7 +391,7 @@ static std::string strip_final_classes(const TagSet& ts, const TagClasses& tc, c
     if (x[p] != '<') continue;
     for (int t = 0; t < ts.n; ++t) {
       int end = 0;
-      if (class_walk(x, n, p, ts, tc, t, true, &end) != 1) continue;
+      if (walk(p, t, &end) != 1) continue;
       auto it = closes.find(key_of(t, p + 1, end - 1));
       if (it == closes.end()) continue;
       auto c = std::lower_bound(it->second.begin(), it->second.end(), end);
@@ -367,7 +410,7 @@ static std::string strip_final_classes(const TagSet& ts, const TagClasses& tc, c
 
 std::string strip_final(const Tags& tags, const uint8_t* x, size_t n) {
   const TagSet& ts = tags.ts;
-  if (tags.kind == TAGS_CLASS) return strip_final_classes(ts, tags.tc, x, (int)n);
+  if (tags.kind == TAGS_CLASS || tags.kind == TAGS_MIXED) return strip_final_classes(tags, x, (int)n);
   // (a pair tag set: the tokens of the folded text — the backreference folds both sides, so a
   // close of the same tag in any case is the open's close, as for ASCII letters)
   struct Tok { int pos, len, id; };

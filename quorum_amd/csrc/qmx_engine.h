@@ -39,7 +39,9 @@ struct Tags {
 // classes: also accept class tags ("." / "[...]" / escaped punctuation; qmx_text.h TagClasses)
 // unicode: also accept non-ASCII tags whose characters are uncased or one of a simple case
 // pair (qmx_unicode_fold.h); a tag set with a pair character is a pair tag set (TagClasses::nfold)
-Tags make_tags(const std::vector<std::string>& tags, bool classes = false, bool unicode = false);
+// mixed: with classes and unicode, also accept class tags and non-ASCII tags in one tag set and
+// both in one tag (`réfl.xion`): a mixed tag set (TagClasses::mixed); without them it means nothing
+Tags make_tags(const std::vector<std::string>& tags, bool classes = false, bool unicode = false, bool mixed = false);
 // the case rule of a non-ASCII tag character: 0 uncased, 1 a pair (*lower: its lower member), 2 refused
 int unicode_tag_char(uint32_t cp, uint32_t* lower);
 uint32_t unicode_tag_partner(uint32_t cp);  // the other member of cp's pair (cp: none)

@@ -486,8 +486,38 @@ __device__ inline int fold_token(const uint8_t* Z, int Zn, int p, const KParams&
   if ((hb & 0x8080808080808080ull) == 0) return 0;
   return fold_match_dev(Z, Zn, p, &P.ts, P.cls);
 }
+// Mixed tag sets (is_mixed_set: a class element and a non-ASCII literal in one set) follow the
+// class rules with the text folded.  The fast matchers still find every tag they can decide by
+// bytes; the tags they cannot — a class element or a pair character (TagClasses::walk) — come
+// from one walk (qmx_text.h mixed_candidate), which tells a class marker from a UTF-8 byte by
+// the tag's bitmap.  A match has the pattern's byte length, so the token model holds.  Returns
+// the walk's token (0: none) or kClsSuspect; out of line as the pair walks are.
+__device__ __noinline__ int mixed_cand_dev(const uint8_t* x, int n, int p, const TagSet* ts, const TagClasses* tc,
+                                           int strip) {
+  int tok = 0, len = 0;
+  const int r = mixed_candidate(x, n, p, *ts, *tc, strip != 0, &tok, &len);
+  return r == CC_SUSPECT ? kClsSuspect : r == CC_MATCH ? tok : 0;
+}
+// class_hold of a mixed tag set: the folded source text outside a block (bit 1 as below), a
+// folded class-aware proper prefix inside one.
+__device__ __noinline__ int mixed_hold_dev(const uint8_t* x, int q, int e, const TagSet* ts, const TagClasses* tc, int dq,
+                                           int tk) {
+  if (dq == 0) {
+    const bool pre = mixed_source_prefix(x, q, e, *ts, *tc);
+    return (pre ? 1 : 0) | (tk > 0 && !pre ? 2 : 0);
+  }
+  return mixed_prefix(x, q, e, *ts, *tc) ? 1 : 0;
+}
+// the first in list order of the fast matchers' token and the walk's
+__device__ __forceinline__ int mixed_first(int lit, int tok) {
+  return tok != 0 && (lit == 0 || abs(tok) < abs(lit)) ? tok : lit;
+}
 __device__ __forceinline__ int class_token(const uint8_t* Z, int Zn, int p, const KParams& P, int lit) {
   if (is_pair_set(*P.cls)) return lit != 0 ? lit : fold_token(Z, Zn, p, P);
+  if (__builtin_expect(is_mixed_set(*P.cls), 0)) {
+    const int tok = mixed_cand_dev(Z, Zn, p, &P.ts, P.cls, 0);
+    return tok == kClsSuspect ? tok : mixed_first(lit, tok);
+  }
   int tok = 0, len = 0;
   const int r = class_candidate(Z, Zn, p, P.ts, *P.cls, false, &tok, &len);
   if (r == CC_SUSPECT) return kClsSuspect;
@@ -502,6 +532,7 @@ __device__ __forceinline__ int class_token(const uint8_t* Z, int Zn, int p, cons
 __device__ __forceinline__ int class_hold(const uint8_t* Z, int q, int e, const KParams& P, int dq, int tk) {
   if (e - q > kMaxTail) return 0;
   if (is_pair_set(*P.cls)) return fold_prefix_dev(Z, q, e, &P.ts, P.cls, dq == 0);
+  if (__builtin_expect(is_mixed_set(*P.cls), 0)) return mixed_hold_dev(Z, q, e, &P.ts, P.cls, dq, tk);
   if (dq == 0) {
     const bool pre = source_prefix(Z, q, e, P.ts, *P.cls);
     return (pre ? 1 : 0) | (tk > 0 && !pre ? 2 : 0);
@@ -2588,6 +2619,15 @@ __device__ __forceinline__ int fin_class_token(const uint8_t* __restrict__ src, 
     if (id != 0) *L = id > 0 ? ts.len[id - 1] + 2 : ts.len[-id - 1] + 3;
     return id;
   }
+  if (__builtin_expect(is_mixed_set(tc), 0)) {  // the byte-literal tags by match_at, the others by the one walk
+    int lit_len = 0;
+    const int lit = match_at(src, n, p, ts, &lit_len);
+    const int tok = mixed_cand_dev(src, n, p, &ts, &tc, 1);
+    if (tok == kClsSuspect) return tok;
+    const int id = mixed_first(lit, tok);
+    if (id != 0) *L = id > 0 ? ts.len[id - 1] + 2 : ts.len[-id - 1] + 3;
+    return id;
+  }
   int lit_len = 0, tok = 0, len = 0;
   const int lit = match_at(src, n, p, ts, &lit_len);
   const int r = class_candidate(src, n, p, ts, tc, true, &tok, &len);
@@ -2611,6 +2651,8 @@ __device__ __forceinline__ int fin_class_token(const uint8_t* __restrict__ src, 
 // Class tags (tc != null): the backreference compares a close with the text its open
 // captured, so the walk by tag id is exact only while every selected close equals that text
 // (ASCII case folded) and no candidate is suspect; otherwise -2 (host path, counted apart).
+// A mixed tag set goes on to the tag's next close instead (the first one equal to the captured
+// text is the regex's too); an open left pending at the end of the text is -2 as well.
 template <bool CLS>
 __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n, const TagSet& ts, int2* __restrict__ segs, int cap,
                           FinShared& F, const TagClasses* tc) {
@@ -2688,10 +2730,19 @@ __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n
             if constexpr (CLS) {  // the close's name against the open's captured bytes, a byte per lane
               wave_fence();  // (FV_PPOS: lane 0's store at the open, maybe a window ago)
               const int ppos = F.v[FV_PPOS], cpos = __shfl(pos, L, 64), nl = ts.len[pend - 1];
-              // (a pair tag set's tags are literal: open and close of one tag fold to the same bytes)
-              const bool ne = lane < nl && !is_pair_set(*tc) &&
+              // (a pair tag set's tags are literal: open and close of one tag fold to the same bytes;
+              // so do the literal characters of a mixed tag set's tags, whose class positions — one
+              // ASCII byte each where no candidate is suspect — are the bytes to compare)
+              const bool cmp = is_mixed_set(*tc) ? (tc->clsmask[pend - 1] >> lane) & 1 : !is_pair_set(*tc);
+              const bool ne = lane < nl && cmp &&
                               lower_ascii(src[ppos + 1 + lane]) != lower_ascii(src[cpos + 2 + lane]);
-              if (__ballot(ne) != 0 && lane == 0) F.v[FV_CLS] = 1;
+              if (__ballot(ne) != 0) {
+                if (__builtin_expect(is_mixed_set(*tc), 0)) {  // not this open's close: on to the tag's next one
+                  cur = cpos + 1;         // (none left: the open stays pending, the host path decides)
+                  continue;
+                }
+                if (lane == 0) F.v[FV_CLS] = 1;
+              }
             }
             cur = __shfl(end, L, 64);
             pend = 0;
@@ -2735,7 +2786,7 @@ __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n
   __syncthreads();
   const int nseg = F.v[FV_NSEG];
   if constexpr (CLS) {
-    if (F.v[FV_CLS] != 0) return -2;
+    if (F.v[FV_CLS] != 0 || F.v[FV_PEND] != 0) return -2;
   }
   return nseg > cap ? -1 : nseg;
 }

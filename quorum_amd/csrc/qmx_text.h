@@ -37,8 +37,10 @@ constexpr int kJsonMaxDepth = 256;  // deeper == RecursionError (stream abort)
 // The three kinds of tag set (host code keeps the kind with the tables: Tags, qmx_engine.h).
 //   literal: ASCII or uncased tags, compared byte for byte (ASCII letters lowercased);
 //   class:   some tag took the class parser (a class element or an escape);
-//   pair:    literal tags with a cased non-ASCII character, the text folded as it is read.
-enum TagKind : int { TAGS_LITERAL, TAGS_CLASS, TAGS_PAIR };
+//   pair:    literal tags with a cased non-ASCII character, the text folded as it is read;
+//   mixed:   a class element and a non-ASCII literal character in one set (make_tags' `mixed`):
+//            the class rules, the text folded as it is read.
+enum TagKind : int { TAGS_LITERAL, TAGS_CLASS, TAGS_PAIR, TAGS_MIXED };
 
 // Class tags (make_tags(tags, classes = true)): the fixed-width part of the regex language
 // the reference's alternation speaks — '.', bracket classes and escaped punctuation.  A tag is
@@ -58,14 +60,27 @@ struct TagClasses {
   // a tag): the tags are literal — n == 0, name[] holds the UTF-8 bytes of the lowercased tag —
   // and the text is folded as it is read: the upper member of a pair stands for its lower
   // member (same byte length).  A character's bytes are packed little-endian, byte k at bit 8k.
-  int nfold;                           // distinct pair characters of the tags; 0: a class tag set
+  int nfold;                           // distinct pair characters of the tags; 0: a class tag set; < 0: a mixed one
   int span;                            // bytes of the longest pattern
   uint8_t fold_len[kMaxFold];
   uint32_t fold_up[kMaxFold], fold_lo[kMaxFold];
+  // Mixed tag sets (make_tags(..., mixed = true), a class element and a non-ASCII literal in one
+  // set): name[] holds lowercase ASCII bytes, the UTF-8 bytes of the lowered non-ASCII literals
+  // and one marker byte 0x80 + class index per class position; len[] counts those bytes.  A
+  // marker is told from a UTF-8 byte by position: bit i of clsmask[t] — name[t][i] is a marker.
+  // walk: bit t — tag t has a class element or a pair character (the byte matchers cannot
+  // decide it).  n and the fold tables are as above; span is unused.  The kind rides in nfold,
+  // the one word the kernels of the class kind read to choose their path: a mixed tag set with
+  // k pair characters keeps -(k + 1) there (mixed_nfold), so a class or pair tag set's device
+  // data, and the loads that decide its path, are what they were.
+  uint32_t walk;
+  uint64_t clsmask[kMaxTags];
 };
-// The kernels of the class kind run class and pair tag sets (KParams::cls is set for both):
-// which of the two the tables are.
+// The kernels of the class kind run class, pair and mixed tag sets (KParams::cls is set for all
+// three): which of them the tables are.
 QMX_HD bool is_pair_set(const TagClasses& tc) { return tc.nfold > 0; }
+QMX_HD bool is_mixed_set(const TagClasses& tc) { return tc.nfold < 0; }
+QMX_HD int mixed_nfold(const TagClasses& tc) { return -tc.nfold - 1; }  // pair characters of a mixed tag set
 
 // (The layout of TagSet is the literal tag sets': the kernels keep a copy in LDS.  The tables
 // of a class or pair tag set travel beside it: Tags::tc on the host, a device copy behind
@@ -327,7 +342,182 @@ QMX_HD bool fold_pattern_prefix(const R& x, int q, int n, const TagSet& ts, cons
 }
 
 // ---------------------------------------------------------------------------
-// the three families behind one kind
+// mixed tags: the class rules, the text folded on read (TAGS_MIXED)
+// ---------------------------------------------------------------------------
+// The character of `ln` bytes packed in `want` (a lowered non-ASCII literal) against the text at
+// x[s:n), folded: equal bytes, or the upper member of the pair whose lower member `want` is.
+// 1: equal;  0: not;  -1: the text ends inside the character and what is there is a prefix of
+// it or of its upper member.  (A mixed tag set's tables: mixed_nfold.)
+template <class R>
+QMX_HD int fold_char_at(const R& x, int n, int s, uint32_t want, int ln, const TagClasses& tc) {
+  const int av = ln < n - s ? ln : n - s;
+  uint32_t have = 0;
+  for (int k = 0; k < av; ++k) have |= (uint32_t)x[s + k] << (8 * k);
+  const uint32_t m = av >= 4 ? 0xffffffffu : ((1u << (8 * av)) - 1u);
+  if (have != (want & m)) {
+    bool ok = false;
+    const int nf = mixed_nfold(tc);
+    for (int f = 0; f < nf; ++f)
+      ok = ok || (tc.fold_len[f] == ln && (tc.fold_up[f] & m) == have && tc.fold_lo[f] == want);
+    if (!ok) return 0;
+  }
+  return av < ln ? -1 : 1;
+}
+QMX_HD int utf8_lead_len(uint8_t c) { return c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : c >= 0xC0 ? 2 : 1; }
+
+// class_walk for a mixed tag set: a class position is one the tag's bitmap names, every other
+// byte >= 0x80 of name[] starts or continues a literal character, compared with the text folded.
+template <class R>
+QMX_HD int mixed_walk(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, int pat, bool strip,
+                      int* end) {
+  const bool close = pat >= ts.n;
+  const int t = close ? pat - ts.n : pat;
+  const uint64_t cm = tc.clsmask[t];
+  int s = p;
+  if (s >= n) return -1;
+  if (x[s] != '<') return 0;
+  ++s;
+  if (close) {
+    if (s >= n) return -1;
+    if (x[s] != '/') return 0;
+    ++s;
+  }
+  for (int i = 0; i < ts.len[t];) {
+    if (s >= n) return -1;
+    const uint8_t c = x[s], e = ts.name[t][i];
+    if ((cm >> i) & 1) {
+      const int k = e - 0x80;
+      if (c < 0x80) {
+        if (!class_accepts(tc, k, c, strip)) return 0;
+        ++s;
+      } else {
+        if (!(tc.flags[k] & CLS_WIDE)) return 0;
+        const int ln = utf8_lead_len(c);
+        if (s + ln > n) return -1;
+        s += ln;
+      }
+      ++i;
+    } else if (e < 0x80) {
+      if (lower_ascii(c) != e) return 0;
+      ++s;
+      ++i;
+    } else {
+      const int ln = utf8_lead_len(e);
+      uint32_t want = 0;
+      for (int k = 0; k < ln; ++k) want |= (uint32_t)ts.name[t][i + k] << (8 * k);
+      const int r = fold_char_at(x, n, s, want, ln, tc);
+      if (r != 1) return r;
+      s += ln;
+      i += ln;
+    }
+  }
+  if (s >= n) return -1;
+  if (x[s] != '>') return 0;
+  *end = s + 1;
+  return 1;
+}
+
+// match_at for a mixed tag set: list order, as class_match_at
+template <class R>
+QMX_HD int mixed_match_at(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, bool strip,
+                          int* tok_len) {
+  if (x[p] != '<') return 0;
+  const bool close = (p + 1 < n && x[p + 1] == '/');
+  for (int t = 0; t < ts.n; ++t) {
+    int end = 0;
+    if (mixed_walk(x, n, p, ts, tc, close ? ts.n + t : t, strip, &end) == 1) {
+      *tok_len = end - p;
+      return close ? -(t + 1) : (t + 1);
+    }
+  }
+  return 0;
+}
+
+// class_candidate for a mixed tag set: the tags the byte matchers cannot decide (TagClasses::walk:
+// a class element or a pair character), pattern bytes in order.  An ASCII literal by lowercase
+// compare, a non-ASCII literal by its folded bytes (never suspect), a class position by its
+// ASCII table; '<', '>' or a byte >= 0x80 AT a class position makes the candidate suspect.  A
+// match has the pattern's byte length.
+template <class R>
+QMX_HD int mixed_candidate(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, bool strip, int* tok,
+                           int* tok_len) {
+  const bool close = p + 1 < n && x[p + 1] == '/';
+  const int s0 = p + (close ? 2 : 1);
+  int res = CC_NONE;
+  for (int t = 0; t < ts.n; ++t) {
+    if (!((tc.walk >> t) & 1)) continue;
+    const int L = ts.len[t];
+    const uint64_t cm = tc.clsmask[t];
+    bool ok = true;
+    for (int i = 0; ok && i < L;) {
+      if (s0 + i >= n) {
+        ok = false;
+        break;
+      }
+      const uint8_t c = x[s0 + i], e = ts.name[t][i];
+      if ((cm >> i) & 1) {
+        if (c == '<' || c == '>' || c >= 0x80) return CC_SUSPECT;
+        ok = class_accepts(tc, e - 0x80, c, strip);
+        ++i;
+      } else if (e < 0x80) {
+        ok = lower_ascii(c) == e;
+        ++i;
+      } else {
+        const int ln = utf8_lead_len(e);
+        uint32_t want = 0;
+        for (int k = 0; k < ln; ++k) want |= (uint32_t)ts.name[t][i + k] << (8 * k);
+        ok = fold_char_at(x, n, s0 + i, want, ln, tc) == 1;
+        i += ln;
+      }
+    }
+    if (ok && res == CC_NONE && s0 + L < n && x[s0 + L] == '>') {
+      res = CC_MATCH;
+      *tok = close ? -(t + 1) : (t + 1);
+      *tok_len = s0 + L + 1 - p;
+    }
+  }
+  return res;
+}
+
+// class_prefix for a mixed tag set
+template <class R>
+QMX_HD bool mixed_prefix(const R& x, int q, int n, const TagSet& ts, const TagClasses& tc) {
+  for (int pat = 0; pat < 2 * ts.n; ++pat) {
+    int end = 0;
+    if (mixed_walk(x, n, q, ts, tc, pat, false, &end) == -1) return true;
+  }
+  return false;
+}
+
+// source_prefix for a mixed tag set: x[q:n), folded, a prefix of "<" + tag source + ">".  A
+// byte >= 0x80 of the source starts a literal character (a bracket class has ASCII members).
+template <class R>
+QMX_HD bool mixed_source_prefix(const R& x, int q, int n, const TagSet& ts, const TagClasses& tc) {
+  const int m = n - q;
+  for (int t = 0; t < ts.n; ++t) {
+    const int L = tc.srclen[t];
+    if (m > L + 2) continue;
+    bool ok = true;
+    for (int i = 0; ok && i < m;) {
+      const uint8_t want = i == 0 ? (uint8_t)'<' : i <= L ? tc.src[t][i - 1] : (uint8_t)'>';
+      if (want < 0x80) {
+        ok = lower_ascii(x[q + i]) == want;
+        ++i;
+        continue;
+      }
+      const int ln = utf8_lead_len(want);
+      uint32_t w = 0;
+      for (int k = 0; k < ln; ++k) w |= (uint32_t)tc.src[t][i - 1 + k] << (8 * k);
+      ok = fold_char_at(x, n, q + i, w, ln, tc) != 0;
+      i += ln;
+    }
+    if (ok) return true;
+  }
+  return false;
+}
+
+// ---------------------------------------------------------------------------
+// the four families behind one kind
 // ---------------------------------------------------------------------------
 // Token at position p of x[0:n), as match_at (strip: a class tag set's final-strip tables).
 template <class R>
@@ -335,6 +525,7 @@ QMX_HD int token_at(TagKind kind, const R& x, int n, int p, const TagSet& ts, co
                     int* tok_len) {
   return kind == TAGS_CLASS ? class_match_at(x, n, p, ts, tc, strip, tok_len)
        : kind == TAGS_PAIR  ? fold_match_at(x, n, p, ts, tc, tok_len)
+       : kind == TAGS_MIXED ? mixed_match_at(x, n, p, ts, tc, strip, tok_len)
                             : match_at(x, n, p, ts, tok_len);
 }
 
@@ -343,6 +534,7 @@ QMX_HD int token_at(TagKind kind, const R& x, int n, int p, const TagSet& ts, co
 template <class R>
 QMX_HD bool held_at(TagKind kind, const R& x, int q, int n, const TagSet& ts, const TagClasses& tc, int depth) {
   if (kind == TAGS_CLASS) return depth == 0 ? source_prefix(x, q, n, ts, tc) : class_prefix(x, q, n, ts, tc);
+  if (kind == TAGS_MIXED) return depth == 0 ? mixed_source_prefix(x, q, n, ts, tc) : mixed_prefix(x, q, n, ts, tc);
   return kind == TAGS_PAIR ? fold_pattern_prefix(x, q, n, ts, tc, depth == 0) : pattern_prefix(x, q, n, ts, depth == 0);
 }
 

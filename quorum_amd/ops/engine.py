@@ -69,7 +69,7 @@ def _unicode_tag_chars_ok(tags: Sequence[str]) -> bool:
 
 
 def native_tag_ok(tags: Sequence[str], max_tags: int = 16, max_len: int = 61, classes: bool = False,
-                  unicode: bool = False) -> bool:
+                  unicode: bool = False, mixed: bool = False) -> bool:
     """Tags the native/GPU matchers run exactly (qmx_text.h): literal printable ASCII, at
     most 16 distinct (lowercased) tags of at most 61 bytes — the MFMA matcher compares a
     16-byte window per '<' and the tail of longer patterns, two 16-pattern column blocks.
@@ -81,7 +81,10 @@ def native_tag_ok(tags: Sequence[str], max_tags: int = 16, max_len: int = 61, cl
 
     ``unicode`` (``runtime.native_unicode_tags``): also non-ASCII tags whose characters are
     uncased or one of a simple case pair (é/É, я/Я); the C++ parser holds the table
-    (``qmx_unicode_fold.h``), the categories no tag may hold (Cn, Cs, Cc) are checked here."""
+    (``qmx_unicode_fold.h``), the categories no tag may hold (Cn, Cs, Cc) are checked here.
+
+    ``mixed`` (``runtime.native_mixed_tags``, with both other keys): also class tags and
+    non-ASCII tags in one tag set, and both in one tag ("réfl.xion")."""
     low = {t.lower() for t in tags}
     if (0 < len(low) <= max_tags
             and all(_PLAIN_TAG.match(t) and not (set(t) & _NOT_PLAIN) and len(t) <= max_len for t in low)):
@@ -93,7 +96,7 @@ def native_tag_ok(tags: Sequence[str], max_tags: int = 16, max_len: int = 61, cl
     from . import native
 
     return native.available() and bool(native.require().tagset_ok([str(t) for t in tags], bool(classes),
-                                                                  bool(unicode)))
+                                                                  bool(unicode), bool(mixed)))
 
 
 class PyEngine:
@@ -199,14 +202,15 @@ def make_engine(kind: str, tags: Sequence[str], device: Optional[int] = None, **
     ``kind``: "auto" | "hip" | "cpu" | "python".  "hip" raises loudly when the HIP
     extension or a GPU is missing (no silent fallback on a GPU box).  ``opts`` go to the
     native engine as they are; a ``grid`` among them must be of the tag set's kind
-    (``native.make_grid(tags, ..., classes=classes, unicode=unicode)``: the class grid for a
-    class tag set and for a pair tag set).
+    (``native.make_grid(tags, ..., classes=classes, unicode=unicode, mixed=mixed)``: the class
+    grid for a class, a pair and a mixed tag set).
     """
     tags = list(tags)
     classes = bool(opts.pop("classes", False))
     unicode = bool(opts.pop("unicode", False))
-    if kind == "python" or not native_tag_ok(tags, classes=classes, unicode=unicode):
-        if kind in ("hip", "cpu") and not native_tag_ok(tags, classes=classes, unicode=unicode):
+    mixed = bool(opts.pop("mixed", False))
+    if kind == "python" or not native_tag_ok(tags, classes=classes, unicode=unicode, mixed=mixed):
+        if kind in ("hip", "cpu") and not native_tag_ok(tags, classes=classes, unicode=unicode, mixed=mixed):
             logger.warning("thinking_tags %r need regex semantics: using the python engine", tags)
         return _py_engine(tags)
     from . import native  # noqa: WPS433 - heavy import deferred
@@ -217,12 +221,14 @@ def make_engine(kind: str, tags: Sequence[str], device: Optional[int] = None, **
             return _py_engine(tags)
         kind = "hip" if native.gpu_available() else "cpu"
     # (the tags as they reach the extension: "[Z-a]" and "[z-a]" are different patterns)
-    key = ((kind, classes, unicode) if classes or unicode else kind,
-           tuple(native.sent_tags(tags, classes, unicode)), -1 if device is None else device)
+    key = ((kind, classes, unicode, mixed) if mixed else (kind, classes, unicode) if classes or unicode else kind,
+           tuple(native.sent_tags(tags, classes, unicode, mixed)), -1 if device is None else device)
     eng = _NATIVE_CACHE.get(key)
     if eng is None:
         if unicode:
             opts["unicode"] = True
+        if mixed:
+            opts["mixed"] = True
         eng = native.NativeEngine(kind, tags, device=device, classes=classes, **opts)
         _NATIVE_CACHE[key] = eng
     return eng

@@ -51,17 +51,20 @@ def gpu_available() -> bool:
         return False
 
 
-def sent_tags(tags: Sequence[str], classes: bool = False, unicode: bool = False) -> List[str]:
+def sent_tags(tags: Sequence[str], classes: bool = False, unicode: bool = False, mixed: bool = False) -> List[str]:
     """The tag list as it is sent to the extension, first occurrence only.  Class and non-ASCII
     tags go down as written (lowercasing would turn "[Z-a]" into another pattern; the C++ parser
     folds non-ASCII tags through its pair table), plain tags through ``str.lower()``, which is
-    more than ASCII lowercasing: "THIN\u212a" (Kelvin sign) is "think" and runs; as written it would not."""
-    return list(dict.fromkeys(t if classes or unicode else t.lower() for t in tags))
+    more than ASCII lowercasing: "THIN\u212a" (Kelvin sign) is "think" and runs; as written it would not.
+    (``mixed`` needs both other keys, so it changes nothing here.)"""
+    return list(dict.fromkeys(t if classes or unicode or mixed else t.lower() for t in tags))
 
 
-def strip_fn(tags: Sequence[str], classes: bool = False, unicode: bool = False) -> Callable[[str, bool], str]:
+def strip_fn(tags: Sequence[str], classes: bool = False, unicode: bool = False,
+             mixed: bool = False) -> Callable[[str, bool], str]:
     ext = require()
-    stripper = ext.Stripper(sent_tags(tags, classes, unicode), classes=bool(classes), unicode=bool(unicode))
+    stripper = ext.Stripper(sent_tags(tags, classes, unicode, mixed), classes=bool(classes), unicode=bool(unicode),
+                            mixed=bool(mixed))
 
     def _strip(text, on):
         if not on:
@@ -74,13 +77,14 @@ def strip_fn(tags: Sequence[str], classes: bool = False, unicode: bool = False) 
 
 
 def make_grid(tags: Sequence[str], device: int, doors: int, wg_per_door: int = 8, idle_ms: int = 50,
-              classes: bool = False, unicode: bool = False):
+              classes: bool = False, unicode: bool = False, mixed: bool = False):
     """A multi-door loop-tick grid (``HipGrid``) of the kind this tag set's engines need: the
-    class kernel for a class tag set (``classes`` on and a '.' or bracket class in a tag) and
-    for a pair tag set (``unicode`` on and a cased non-ASCII character in a tag), the literal
+    class kernel for a class tag set (``classes`` on and a '.' or bracket class in a tag), for
+    a pair tag set (``unicode`` on and a cased non-ASCII character in a tag) and for a mixed tag
+    set (``mixed`` on with both, class elements and non-ASCII literals in one set), the literal
     kernel otherwise.  Every ``NativeEngine`` given the grid must use the same tags."""
     ext = require()
-    cls = bool(classes or unicode) and ext.tagset_has_classes(list(tags), bool(classes), bool(unicode))
+    cls = bool(classes or unicode) and ext.tagset_has_classes(list(tags), bool(classes), bool(unicode), bool(mixed))
     return ext.HipGrid(device, doors, wg_per_door, idle_ms, classes=cls)
 
 
@@ -89,14 +93,16 @@ class NativeEngine:
 
     def __init__(self, kind: str, tags: Sequence[str], device: Optional[int] = None,
                  tile_bytes: int = 16384, max_slots: int = 8192, content_cap: int = 1 << 20, lanes: int = 1,
-                 grid=None, door: int = -1, ndoors: int = 1, classes: bool = False, unicode: bool = False):
+                 grid=None, door: int = -1, ndoors: int = 1, classes: bool = False, unicode: bool = False,
+                 mixed: bool = False):
         ext = require()
         self.kind = kind
         self.name = kind
         self.tags: List[str] = list(tags)
         self.classes = bool(classes)
         self.unicode = bool(unicode)
-        low = sent_tags(tags, classes, unicode)
+        self.mixed = bool(mixed)
+        low = sent_tags(tags, classes, unicode, mixed)
         if kind == "hip":
             if ext.device_count() <= 0:
                 raise RuntimeError("engine 'hip' requested but no GPU is visible")
@@ -105,10 +111,10 @@ class NativeEngine:
             # grid: a HipGrid (loop ticks) — this engine posts its ticks into door `door` of it.
             # A class tag set needs a grid made with classes=True (make_grid picks the kind)
             self._e = ext.HipEngine(low, device, tile_bytes, max_slots, content_cap, lanes, grid, door, ndoors,
-                                     classes=self.classes, unicode=self.unicode)
+                                     classes=self.classes, unicode=self.unicode, mixed=self.mixed)
             self.offload = True
         else:
-            self._e = ext.CpuEngine(low, classes=self.classes, unicode=self.unicode)
+            self._e = ext.CpuEngine(low, classes=self.classes, unicode=self.unicode, mixed=self.mixed)
             self.offload = False
         self.open = self._e.open
         self.feed = self._e.feed

@@ -8,7 +8,9 @@
 //    default tags and with class tag sets ('.', "[...]", escapes: make_tags(tags, true)),
 //    their pieces including multi-byte code points and '<' / '>' at class positions, and with
 //    non-ASCII tag sets (make_tags(tags, false, true): uncased and case-pair characters, the
-//    text folded on read), their pieces in both cases, look-alikes and JSON-escaped forms;
+//    text folded on read), their pieces in both cases, look-alikes and JSON-escaped forms,
+//    and with mixed tag sets (make_tags(tags, true, true, true): class elements and non-ASCII
+//    literals in one set and in one tag);
 //  * strip_final idempotence on already-stripped text and JSON DOM round-trips
 //    (parse(dump(parse(x))) == parse(x)), py_float_repr/escape on random inputs;
 //  * everything runs under -fsanitize=address,undefined: any OOB / UB aborts the run.
@@ -40,6 +42,7 @@ struct ClassSet {
   std::vector<std::string> tags;
   std::vector<const char*> pieces;
   bool unicode = false;  // a non-ASCII tag set (make_tags' `unicode`), no class tags
+  bool mixed = false;    // a mixed tag set (make_tags' `classes`, `unicode` and `mixed`)
 };
 const ClassSet kClassSets[] = {
     {{"think", "th.nk"},
@@ -60,6 +63,17 @@ const ClassSet kClassSets[] = {
     {{"思考", "a思考过程分"},
      {"<思考>", "</思考>", "<a思考过程分>", "</A思考过程分>", "</a思考过程切>", "<a思考", "过程分>", "<\\u601d", "\\u8003>"},
      true},
+    // mixed tag sets: class and pair in separate tags; both in one tag, a non-ASCII first element
+    {{"think", "réflexion", "t[0-9]", "思考"},
+     {"<réflexion>", "</RÉFLEXION>", "<R\\u00c9flexion>", "<rèflexion>", "<RÉ", "flexion>", "<t4>", "</T7>", "<t", "4>", "<tx>",
+      "<t\xc3\xa9>", "<t<>", "<t>>", "<思考>", "</\\u601d\\u8003>", "<思", "考>", "<think>", "</THINK>"},
+     true, true},
+    {{"réfl.xion", "思[0-9]", "é.", "abcdefghijklmn.я"},
+     {"<réfl0xion>", "</RÉFL0XION>", "<R\\u00c9FLxXION>", "<réfl.xion>", "<réfl", "0xion>", ".xion>", "<réfl\xc3\xa9xion>",
+      "</réfl\xc3\x89xion>", "<réfl<xion>", "<réfl>xion>", "<réfl\\nxion>", "<思7>", "</思8>", "<思", "7>", "<思\xc3\xa9>", "<怞7>",
+      "<é1>", "</É1>", "<é>>", "</é\xe4\xb8\xad>", "<\\u00c9", "x>", "<abcdefghijklmn7я>", "</ABCDEFGHIJKLMNxЯ>",
+      "<abcdefghijklmn", ".я>", "7\\u042f>", "<abcdefghijklmn\xe4\xb8\xadя>"},
+     true, true},
 };
 const ClassSet* g_class = nullptr;  // the class tag set of this iteration (null: the default tags)
 
@@ -196,8 +210,9 @@ int main(int argc, char** argv) {
   for (int it = 0; it < iters; ++it) {
     // every other iteration: one of the class tag sets
     g_class = it % 2 ? &kClassSets[(it / 2) % (int)(sizeof(kClassSets) / sizeof(kClassSets[0]))] : nullptr;
-    const Tags tags = make_tags(g_class ? g_class->tags : default_tags, g_class != nullptr && !g_class->unicode,
-                                g_class != nullptr && g_class->unicode);
+    const Tags tags = make_tags(g_class ? g_class->tags : default_tags,
+                                g_class != nullptr && (!g_class->unicode || g_class->mixed),
+                                g_class != nullptr && g_class->unicode, g_class != nullptr && g_class->mixed);
     int ns = 1 + R(4);
     std::vector<std::string> bodies;
     std::vector<bool> filt;

@@ -295,6 +295,11 @@ class RuntimeConfig:
                ß, ı, İ, å, combining marks of case expansions), control and unassigned code
                points, and a tag set that also has a class tag are refused: those still need the
                python engine.  Off (the default): any non-ASCII tag does
+    native_mixed_tags: with native_regex_tags and native_unicode_tags both on (refused otherwise),
+               class tags and non-ASCII tags also run in one tag set, and both in one tag
+               ("réfl.xion", "思[0-9]", "é."): the class rules, the text folded as it is read.  A
+               non-ASCII member of a bracket class ("a[é]") is still refused.  Off (the default):
+               such a tag list needs the python engine
     """
 
     engine: str = "auto"
@@ -320,12 +325,18 @@ class RuntimeConfig:
     light_host_sessions: Optional[int] = None
     native_regex_tags: bool = False
     native_unicode_tags: bool = False
+    native_mixed_tags: bool = False
 
     def __post_init__(self):
         if not isinstance(self.native_regex_tags, bool):
             raise ValueError(f"runtime.native_regex_tags must be true or false, got {self.native_regex_tags!r}")
         if not isinstance(self.native_unicode_tags, bool):
             raise ValueError(f"runtime.native_unicode_tags must be true or false, got {self.native_unicode_tags!r}")
+        if not isinstance(self.native_mixed_tags, bool):
+            raise ValueError(f"runtime.native_mixed_tags must be true or false, got {self.native_mixed_tags!r}")
+        if self.native_mixed_tags and not (self.native_regex_tags and self.native_unicode_tags):
+            raise ValueError("runtime.native_mixed_tags needs runtime.native_regex_tags and "
+                             "runtime.native_unicode_tags both true")
 
     @classmethod
     def from_config(cls, cfg: Dict[str, Any]) -> "RuntimeConfig":

@@ -73,6 +73,9 @@ def main():
                     help="non-ASCII tags (runtime.native_unicode_tags), e.g. --tags think,思考 (a literal tag set: "
                          "the literal kernels) or --tags think,réflexion (a pair tag set: the class kernels, with "
                          "--grid N a class grid)")
+    ap.add_argument("--mixed", action="store_true",
+                    help="with --classes and --unicode: class and non-ASCII tags in one set (runtime.native_mixed_tags), "
+                         "e.g. --tags think,réflexion,t[0-9] or --tags think,réfl.xion (a mixed tag set: the class kernels)")
     ap.add_argument("--body-tag", default="think",
                     help="mock shape: the think block's tag as the upstream writes it, e.g. réflexion or RÉFLEXION")
     args = ap.parse_args()
@@ -89,7 +92,7 @@ def main():
         # a class tag set runs on a grid of its own kind (the class kernel)
         # (so does a pair tag set: --unicode and a cased non-ASCII character in a tag)
         grid = ext.HipGrid(0, args.grid, 8, classes=(args.classes or args.unicode)
-                           and ext.tagset_has_classes(tags, args.classes, args.unicode))
+                           and ext.tagset_has_classes(tags, args.classes, args.unicode, args.mixed))
     combos = {"ft": (True, True), "f": (True, False), "t": (False, True)}
     for filt, emit in [combos[c] for c in args.combos.split(",")]:
         for n in [int(x) for x in args.slots.split(",")]:
@@ -98,6 +101,8 @@ def main():
                 kw["classes"] = True
             if args.unicode:
                 kw["unicode"] = True
+            if args.mixed:
+                kw["mixed"] = True
             eng = NativeEngine(args.engine, tags, device=0, max_slots=4096, content_cap=1 << 16, **kw)
             walls = []
             evs = [e + b"\n\n" for e in body.split(b"\n\n") if e]
