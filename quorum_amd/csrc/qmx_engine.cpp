@@ -25,6 +25,7 @@ struct Elem {
   uint8_t lit = 0;
   uint32_t tab[4] = {0, 0, 0, 0};
   uint8_t flags = 0;
+  std::string txt;  // as written (a plain literal lowered): tagset_rows
 };
 
 bool printable(uint8_t c) { return c >= 0x20 && c < 0x7f; }
@@ -87,38 +88,155 @@ bool parse_bracket(const std::string& t, size_t& i, Elem& e) {
   return true;
 }
 
-// The elements of one tag, or false when it lies outside the class subset.  wide: a byte
-// >= 0x80 outside a bracket class is a literal element of its own (a mixed tag set: the bytes of
-// a non-ASCII literal character, already lowered through the pair table).
+// One element of a class tag at t[i] (a literal, an escape, '.', a bracket class), or false when
+// it lies outside the class subset.  wide: a byte >= 0x80 outside a bracket class is a literal
+// element of its own (a mixed tag set: the bytes of a non-ASCII literal character, already
+// lowered through the pair table).
+bool parse_elem(const std::string& t, size_t& i, Elem& e, bool wide) {
+  const uint8_t c = (uint8_t)t[i];
+  const size_t i0 = i;
+  if (c == '\\') {
+    if (i + 1 >= t.size() || !std::strchr(".^$*+?{}[]\\|()-", t[i + 1])) return false;
+    e.lit = (uint8_t)t[i + 1];
+    i += 2;
+  } else if (c == '.') {
+    e.cls = true;
+    e.flags = CLS_WIDE | CLS_DOT;
+    for (int k = 0; k < 4; ++k) e.tab[k] = ~0u;
+    ++i;
+  } else if (c == '[') {
+    if (!parse_bracket(t, i, e)) return false;
+  } else if (wide && c >= 0x80) {
+    e.lit = c;
+    ++i;
+  } else {
+    if (!printable(c) || std::strchr("^$*+?{}]|()<>/", (int)c)) return false;
+    e.lit = lower_ascii(c);
+    ++i;
+  }
+  e.txt = t.substr(i0, i - i0);
+  if (!e.cls && e.txt.size() == 1) e.txt[0] = (char)e.lit;
+  return true;
+}
+
+// The elements of one tag, or false when it lies outside the class subset.
 bool parse_class_tag(const std::string& t, std::vector<Elem>& out, bool wide = false) {
   for (size_t i = 0; i < t.size();) {
-    const uint8_t c = (uint8_t)t[i];
     Elem e;
-    if (c == '\\') {
-      if (i + 1 >= t.size() || !std::strchr(".^$*+?{}[]\\|()-", t[i + 1])) return false;
-      e.lit = (uint8_t)t[i + 1];
-      i += 2;
-    } else if (c == '.') {
-      e.cls = true;
-      e.flags = CLS_WIDE | CLS_DOT;
-      for (int k = 0; k < 4; ++k) e.tab[k] = ~0u;
-      ++i;
-    } else if (c == '[') {
-      if (!parse_bracket(t, i, e)) return false;
-    } else if (wide && c >= 0x80) {
-      e.lit = c;
-      ++i;
-    } else {
-      if (!printable(c) || std::strchr("^$*+?{}]|()<>/", (int)c)) return false;
-      e.lit = lower_ascii(c);
-      ++i;
-    }
+    if (!parse_elem(t, i, e, wide)) return false;
     out.push_back(e);
   }
   return !out.empty() && !out[0].cls;
 }
 
+// Variable-width tags (make_tags' `variants`): the class subset plus '?' after an element or a
+// group, '|' and groups "(...)" / "(?:...)".  Such a tag has the matches of the ordered
+// alternation of its fixed-width expansions, its rows: "x?" is "(?:x|)" (greedy: present
+// first), concatenation distributes over ordered alternation and keeps the priority order, and
+// a backtracking matcher returns the first success in that order.  A recursive-descent parser
+// over alt := seq ('|' seq)*, seq := (atom '?'?)*, atom := element | group.
+typedef std::vector<Elem> Row;
+typedef std::vector<Row> Rows;  // in priority order, no two equal
+
+bool same_elem(const Elem& a, const Elem& b) {
+  if (a.cls != b.cls) return false;
+  return a.cls ? a.flags == b.flags && std::memcmp(a.tab, b.tab, sizeof(a.tab)) == 0 : a.lit == b.lit;
+}
+bool same_row(const Row& a, const Row& b) {
+  if (a.size() != b.size()) return false;
+  for (size_t i = 0; i < a.size(); ++i)
+    if (!same_elem(a[i], b[i])) return false;
+  return true;
+}
+
+struct TooManyRows {};
+
+// A later duplicate of a row never matches where the first did not: dropped.  The count of
+// distinct rows only grows towards the whole tag, so more than kMaxTags here is more at the end.
+void add_row(Rows& rows, const Row& r) {
+  for (const Row& have : rows)
+    if (same_row(have, r)) return;
+  if ((int)rows.size() >= kMaxTags) throw TooManyRows();
+  rows.push_back(r);
+}
+
+struct VariantParser {
+  const std::string& t;
+  bool wide;
+  size_t i = 0;
+  bool ops = false;  // a '?', a '|' or a group was read: a variable-width tag
+
+  bool alt(Rows& out, int depth) {
+    do {
+      Rows s;
+      if (!seq(s, depth)) return false;
+      for (const Row& r : s) add_row(out, r);
+      if (i >= t.size() || t[i] != '|') return true;
+      ops = true;
+      ++i;
+    } while (true);
+  }
+  bool seq(Rows& out, int depth) {
+    out.assign(1, Row());
+    while (i < t.size() && t[i] != '|' && t[i] != ')') {
+      Rows a;
+      if (t[i] == '(') {
+        if (depth >= kMaxTagLen) return false;
+        ops = true;
+        ++i;
+        if (i < t.size() && t[i] == '?') {
+          if (i + 1 >= t.size() || t[i + 1] != ':') return false;
+          i += 2;
+        }
+        if (!alt(a, depth + 1) || i >= t.size() || t[i] != ')') return false;
+        ++i;
+      } else {
+        Elem e;
+        if (!parse_elem(t, i, e, wide)) return false;
+        a.assign(1, Row(1, e));
+      }
+      if (i < t.size() && t[i] == '?') {  // greedy: present, then absent; "??", "?+", "?*", "?{" are refused
+        ops = true;
+        ++i;
+        if (i < t.size() && std::strchr("?+*{", t[i])) return false;
+        add_row(a, Row());
+      }
+      Rows next;
+      for (const Row& l : out)
+        for (const Row& r : a) {
+          Row c = l;
+          c.insert(c.end(), r.begin(), r.end());
+          add_row(next, c);
+        }
+      out.swap(next);
+    }
+    return true;
+  }
+};
+
+// The rows of one tag; *ops: it is a variable-width tag.  False outside the subset.
+bool parse_variant_tag(const std::string& t, Rows& out, bool wide, bool* ops) {
+  VariantParser p{t, wide};
+  if (!p.alt(out, 0) || p.i != t.size()) return false;
+  *ops = p.ops;
+  return true;
+}
+
+Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants,
+                std::vector<std::pair<std::string, int>>* rows_out);
+
 }  // namespace
+
+Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants) {
+  return build_tags(tags, classes, unicode, mixed, variants, nullptr);
+}
+
+std::vector<std::pair<std::string, int>> tagset_rows(const std::vector<std::string>& tags, bool classes, bool unicode,
+                                                     bool mixed, bool variants) {
+  std::vector<std::pair<std::string, int>> rows;
+  build_tags(tags, classes, unicode, mixed, variants, &rows);
+  return rows;
+}
 
 // The case rule of a non-ASCII tag character (qmx_unicode_fold.h, generated from the rule in
 // tools/gen_unicode_fold.py).  0: uncased, 1: a pair (*lower: its lower member, which may be
@@ -146,8 +264,11 @@ uint32_t unicode_tag_partner(uint32_t cp) {
   return cp;
 }
 
-Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed) {
+namespace {
+Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants,
+                std::vector<std::pair<std::string, int>>* rows_out) {
   mixed = mixed && classes && unicode;
+  variants = variants && classes;
   Tags out;
   std::memset(&out, 0, sizeof(out));
   TagSet& ts = out.ts;
@@ -155,6 +276,8 @@ Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode,
   bool any_cls = false, any_wide = false;
   uint32_t pair_tags = 0;  // bit t: tag t holds a pair character
   std::vector<std::string> seen;
+  std::vector<Row> row_pat;  // variants: every row's pattern, and the tag it comes from
+  std::vector<std::string> row_tag;
   auto pack = [](uint32_t cp, int* len) {  // UTF-8 bytes, byte k at bit 8k
     uint8_t b[4];
     *len = put_wtf8(cp, b);
@@ -162,7 +285,8 @@ Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode,
     for (int k = 0; k < *len; ++k) v |= (uint32_t)b[k] << (8 * k);
     return v;
   };
-  for (const auto& t0 : tags) {
+  for (size_t ti = 0; ti < tags.size(); ++ti) {
+    const std::string& t0 = tags[ti];
     std::string t, tw;  // tw: the tag as written, its non-ASCII characters lowered (mixed: the class parser's input)
     bool wide = false, has_pair = false;
     for (char c : t0) wide = wide || (uint8_t)c >= 0x80;
@@ -219,47 +343,94 @@ Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode,
       if (!literal) throw std::invalid_argument("tag needs regex semantics: " + t0);
       throw std::invalid_argument("unsupported tag length: " + t0);
     }
-    std::vector<Elem> elems;
+    Rows rows(1);
+    bool var = false;  // a variable-width tag: '?', '|' or a group
     if (!literal) {
       // class tags: '.', [...] and escaped punctuation, one code point per element; the
       // tables come from the tag as written (IGNORECASE makes its case immaterial)
       const bool mix = mixed && wide;  // a class element and a non-ASCII literal in one tag
-      if (!classes || !parse_class_tag(mix ? tw : t0, elems, mix)) throw std::invalid_argument("tag needs regex semantics: " + t0);
-      int bound = 3;  // bytes of the longest "</" + match + ">"
-      for (const Elem& e : elems) bound += (e.flags & CLS_WIDE) ? 4 : 1;
-      if (bound > kMaxTail) throw std::invalid_argument("unsupported tag length: " + t0);
-    }
-    if (ts.n >= kMaxTags) throw std::invalid_argument("too many thinking tags");
-    seen.push_back(t);
-    any_wide = any_wide || wide;  // (a bracket class has ASCII members: every byte >= 0x80 is a literal's)
-    if (has_pair) pair_tags |= 1u << ts.n;
-    tc.srclen[ts.n] = (int)t.size();
-    std::memcpy(tc.src[ts.n], t.data(), t.size());
-    if (literal) {
-      ts.len[ts.n] = (int)t.size();
-      std::memcpy(ts.name[ts.n], t.data(), t.size());
-    } else {
-      any_cls = true;
-      ts.len[ts.n] = (int)elems.size();
-      for (size_t i = 0; i < elems.size(); ++i) {
-        const Elem& e = elems[i];
-        if (!e.cls) {
-          ts.name[ts.n][i] = e.lit;
-          continue;
+      bool ok = classes;
+      if (ok && variants) {
+        // (a non-ASCII variable-width tag without `mixed` gets the mixing message below)
+        const bool w = wide && unicode;
+        rows.clear();
+        try {
+          ok = parse_variant_tag(w ? tw : t0, rows, w, &var);
+        } catch (const TooManyRows&) {
+          throw std::invalid_argument("thinking tags expand to more than 16 rows: " + t0);
         }
-        tc.clsmask[ts.n] |= 1ull << i;
-        int k = 0;
-        while (k < tc.n && !(tc.flags[k] == e.flags && std::memcmp(tc.tab[k], e.tab, sizeof(e.tab)) == 0)) ++k;
-        if (k == tc.n) {
-          if (tc.n >= kMaxClasses) throw std::invalid_argument("too many tag classes");
-          std::memcpy(tc.tab[k], e.tab, sizeof(e.tab));
-          tc.flags[k] = e.flags;
-          ++tc.n;
-        }
-        ts.name[ts.n][i] = (uint8_t)(0x80 + k);
+        if (ok && !var) ok = (mix || !wide) && !rows[0].empty() && !rows[0][0].cls;
+      } else if (ok) {
+        ok = parse_class_tag(mix ? tw : t0, rows[0], mix);
+      }
+      if (!ok) throw std::invalid_argument("tag needs regex semantics: " + t0);
+      for (const Row& elems : rows) {
+        if (elems.empty()) throw std::invalid_argument("tag has an empty alternative: " + t0);
+        if (elems[0].cls) throw std::invalid_argument("tag has an alternative that begins with a class: " + t0);
+        int bound = 3;  // bytes of the longest "</" + match + ">"
+        for (const Elem& e : elems) bound += (e.flags & CLS_WIDE) ? 4 : 1;
+        if (bound > kMaxTail) throw std::invalid_argument("unsupported tag length: " + t0);
       }
     }
-    ++ts.n;
+    seen.push_back(t);
+    any_wide = any_wide || wide;  // (a bracket class has ASCII members: every byte >= 0x80 is a literal's)
+    any_cls = any_cls || var;     // (its source text is not its pattern: of the class kind)
+    for (const Row& elems : rows) {
+      if (variants) {
+        // the depth-0 holdback keeps ONE source text per pattern: the same pattern from a
+        // variable-width tag and from another tag would need both
+        Row pat = elems;
+        if (literal)
+          for (char ch : t) {
+            Elem e;
+            e.lit = (uint8_t)ch;
+            pat.push_back(e);
+          }
+        for (size_t j = 0; j < row_pat.size(); ++j)
+          if (same_row(row_pat[j], pat) && (var || (tc.var >> j) & 1))
+            throw std::invalid_argument("two thinking tags give the same pattern under different source texts: " +
+                                        row_tag[j] + ", " + t0);
+        row_pat.push_back(pat);
+        row_tag.push_back(t0);
+      }
+      if (ts.n >= kMaxTags)
+        throw std::invalid_argument(var || tc.var ? "thinking tags expand to more than 16 rows: " + t0
+                                                  : std::string("too many thinking tags"));
+      if (var) tc.var |= 1u << ts.n;
+      if (rows_out) {
+        std::string txt = literal ? t : std::string();
+        for (const Elem& e : elems) txt += e.txt;
+        rows_out->emplace_back(txt, (int)ti);
+      }
+      if (has_pair) pair_tags |= 1u << ts.n;
+      tc.srclen[ts.n] = (int)t.size();
+      std::memcpy(tc.src[ts.n], t.data(), t.size());
+      if (literal) {
+        ts.len[ts.n] = (int)t.size();
+        std::memcpy(ts.name[ts.n], t.data(), t.size());
+      } else {
+        any_cls = true;
+        ts.len[ts.n] = (int)elems.size();
+        for (size_t i = 0; i < elems.size(); ++i) {
+          const Elem& e = elems[i];
+          if (!e.cls) {
+            ts.name[ts.n][i] = e.lit;
+            continue;
+          }
+          tc.clsmask[ts.n] |= 1ull << i;
+          int k = 0;
+          while (k < tc.n && !(tc.flags[k] == e.flags && std::memcmp(tc.tab[k], e.tab, sizeof(e.tab)) == 0)) ++k;
+          if (k == tc.n) {
+            if (tc.n >= kMaxClasses) throw std::invalid_argument("too many tag classes");
+            std::memcpy(tc.tab[k], e.tab, sizeof(e.tab));
+            tc.flags[k] = e.flags;
+            ++tc.n;
+          }
+          ts.name[ts.n][i] = (uint8_t)(0x80 + k);
+        }
+      }
+      ++ts.n;
+    }
   }
   if (ts.n == 0) throw std::invalid_argument("empty tag set");
   // a class position is kept as byte 0x80 + k in TagSet::name, where a non-ASCII tag keeps
@@ -282,6 +453,7 @@ Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode,
   if (out.kind == TAGS_LITERAL) std::memset(&tc, 0, sizeof(tc));
   return out;
 }
+}  // namespace
 
 // --------------------------------------------------------------------------------
 // streaming filter: state (depth, tail); X = tail ++ text, token walk left to right

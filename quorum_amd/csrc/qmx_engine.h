@@ -41,7 +41,17 @@ struct Tags {
 // pair (qmx_unicode_fold.h); a tag set with a pair character is a pair tag set (TagClasses::nfold)
 // mixed: with classes and unicode, also accept class tags and non-ASCII tags in one tag set and
 // both in one tag (`réfl.xion`): a mixed tag set (TagClasses::mixed); without them it means nothing
-Tags make_tags(const std::vector<std::string>& tags, bool classes = false, bool unicode = false, bool mixed = false);
+// variants: with classes, also accept variable-width tags — '?' after an element or a group, '|'
+// and groups "(...)" / "(?:...)".  Such a tag becomes its rows, the fixed-width expansions in
+// the regex's priority order (`think(ing)?`: thinking, think), one entry of the set each (at
+// most 16 per set), all with the tag's own source text (TagClasses::var); the set is of the
+// class kind, or of the mixed kind when it holds a non-ASCII character (which needs `mixed`)
+Tags make_tags(const std::vector<std::string>& tags, bool classes = false, bool unicode = false, bool mixed = false,
+               bool variants = false);
+// The rows of the set make_tags builds, in order, as text (a class position as "." or "[]"),
+// each with the index of its tag in `tags` (tests, tools/kbench.py)
+std::vector<std::pair<std::string, int>> tagset_rows(const std::vector<std::string>& tags, bool classes = false,
+                                                     bool unicode = false, bool mixed = false, bool variants = false);
 // the case rule of a non-ASCII tag character: 0 uncased, 1 a pair (*lower: its lower member), 2 refused
 int unicode_tag_char(uint32_t cp, uint32_t* lower);
 uint32_t unicode_tag_partner(uint32_t cp);  // the other member of cp's pair (cp: none)

@@ -3702,7 +3702,7 @@ int run_server(const ServerCfg& cfg0) {
   g_drain.store(false);
   g_ready.store(0);
   // the one tag set of this server: every engine, the verify shadows and the loops share it
-  const Tags tags = make_tags(cfg.tags, cfg.tag_classes, cfg.tag_unicode, cfg.tag_mixed);
+  const Tags tags = make_tags(cfg.tags, cfg.tag_classes, cfg.tag_unicode, cfg.tag_mixed, cfg.tag_variants);
   std::vector<std::unique_ptr<Loop>> loops;
   std::vector<std::thread> ts;
   for (int i = 0; i < std::max(1, cfg.threads); ++i) loops.emplace_back(new Loop(cfg, i, tags));
@@ -3724,7 +3724,8 @@ int run_server(const ServerCfg& cfg0) {
   // is made with the flag and launches the kernel that carries the class paths
   // (qmx_ctick_persistent); the loops' engines carry the same tag set, so they pair with it.
   // (a pair tag set, runtime.native_unicode_tags, is of the class kind: its text is folded on read;
-  // so is a mixed one, runtime.native_mixed_tags)
+  // so is a mixed one, runtime.native_mixed_tags, and a set with a variable-width tag,
+  // runtime.native_variant_tags)
   const bool cls_tags = tags.kind != TAGS_LITERAL;
   const bool loop_ticks = hip && cfg.tick_mode != "lanes" && cfg.shared_engine != 1;
   const bool shared = !loop_ticks && (cfg.shared_engine < 0 ? hip : cfg.shared_engine > 0);

@@ -75,6 +75,12 @@ struct TagClasses {
   // data, and the loads that decide its path, are what they were.
   uint32_t walk;
   uint64_t clsmask[kMaxTags];
+  // Variable-width tags (make_tags(..., variants = true): '?', '|' and groups).  Such a tag is
+  // kept as its rows — its fixed-width expansions in the regex's priority order, one entry of
+  // TagSet each, src[] of every one the tag's whole source text.  var: bit r — row r comes from
+  // such a tag; 0 for every other set.  The last field, read only where a class position holds
+  // '<', '>' or a byte >= 0x80 (variant_mismatch): the other sets' data and loads are what they were.
+  uint32_t var;
 };
 // The kernels of the class kind run class, pair and mixed tag sets (KParams::cls is set for all
 // three): which of them the tables are.
@@ -217,7 +223,17 @@ QMX_HD int class_match_at(const R& x, int n, int p, const TagSet& ts, const TagC
 // exact host path decides the stream.  CC_MATCH: the first tag in list order that matches,
 // every class position one ASCII byte (*tok, *tok_len as match_at).  Text that ends before a
 // pattern does is no match here (the holdback's prefix tests look at it).
+// A set with a variable-width tag (TagClasses::var): such a byte at a class position is a plain
+// mismatch of that row where the exact walk returns 0 — a '<' or '>' the class's table does not
+// accept, a byte >= 0x80 at a class that is not CLS_WIDE.  The rows of `t[0-9]?` are `t[0-9]`
+// and `t`: the '>' of every plain "<t>" lies on the class position of the first.  A byte the
+// class accepts stays suspect.
 enum : int { CC_NONE = 0, CC_MATCH = 1, CC_SUSPECT = 2 };
+// c: '<', '>' or >= 0x80 at a position of class k — a mismatch (not a suspect) of the row?
+QMX_HD bool variant_mismatch(const TagClasses& tc, int k, uint8_t c) {
+  if (tc.var == 0) return false;
+  return c >= 0x80 ? !(tc.flags[k] & CLS_WIDE) : !((tc.tab[k][c >> 5] >> (c & 31)) & 1u);
+}
 template <class R>
 QMX_HD int class_candidate(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, bool strip, int* tok,
                            int* tok_len) {
@@ -237,8 +253,10 @@ QMX_HD int class_candidate(const R& x, int n, int p, const TagSet& ts, const Tag
       }
       const uint8_t c = x[s0 + i], e = ts.name[t][i];
       if (e < 0x80) ok = lower_ascii(c) == e;
-      else if (c == '<' || c == '>' || c >= 0x80) return CC_SUSPECT;
-      else ok = class_accepts(tc, e - 0x80, c, strip);
+      else if (c == '<' || c == '>' || c >= 0x80) {
+        if (!variant_mismatch(tc, e - 0x80, c)) return CC_SUSPECT;
+        ok = false;
+      } else ok = class_accepts(tc, e - 0x80, c, strip);
     }
     if (ok && res == CC_NONE && s0 + L < n && x[s0 + L] == '>') {
       res = CC_MATCH;
@@ -456,8 +474,12 @@ QMX_HD int mixed_candidate(const R& x, int n, int p, const TagSet& ts, const Tag
       }
       const uint8_t c = x[s0 + i], e = ts.name[t][i];
       if ((cm >> i) & 1) {
-        if (c == '<' || c == '>' || c >= 0x80) return CC_SUSPECT;
-        ok = class_accepts(tc, e - 0x80, c, strip);
+        if (c == '<' || c == '>' || c >= 0x80) {
+          if (!variant_mismatch(tc, e - 0x80, c)) return CC_SUSPECT;
+          ok = false;
+        } else {
+          ok = class_accepts(tc, e - 0x80, c, strip);
+        }
         ++i;
       } else if (e < 0x80) {
         ok = lower_ascii(c) == e;

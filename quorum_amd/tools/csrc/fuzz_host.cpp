@@ -10,7 +10,12 @@
 //    non-ASCII tag sets (make_tags(tags, false, true): uncased and case-pair characters, the
 //    text folded on read), their pieces in both cases, look-alikes and JSON-escaped forms,
 //    and with mixed tag sets (make_tags(tags, true, true, true): class elements and non-ASCII
-//    literals in one set and in one tag);
+//    literals in one set and in one tag), and with variable-width tag sets (make_tags(tags, true,
+//    ..., true): '?', '|' and groups, every tag its rows), their pieces every row in both cases,
+//    the source texts cut short, '>' and non-ASCII at the optional class positions;
+//  * malformed tags: random strings over the tag grammar's alphabet — unbalanced '(', a trailing
+//    '|', "(?", a depth of 100 among them — fed to make_tags with every key on either are accepted
+//    or throw std::invalid_argument, and never crash (the parser is recursive code over user input);
 //  * strip_final idempotence on already-stripped text and JSON DOM round-trips
 //    (parse(dump(parse(x))) == parse(x)), py_float_repr/escape on random inputs;
 //  * everything runs under -fsanitize=address,undefined: any OOB / UB aborts the run.
@@ -43,6 +48,7 @@ struct ClassSet {
   std::vector<const char*> pieces;
   bool unicode = false;  // a non-ASCII tag set (make_tags' `unicode`), no class tags
   bool mixed = false;    // a mixed tag set (make_tags' `classes`, `unicode` and `mixed`)
+  bool variants = false;  // variable-width tags (make_tags' `variants`, with `classes`)
 };
 const ClassSet kClassSets[] = {
     {{"think", "th.nk"},
@@ -74,6 +80,21 @@ const ClassSet kClassSets[] = {
       "<é1>", "</É1>", "<é>>", "</é\xe4\xb8\xad>", "<\\u00c9", "x>", "<abcdefghijklmn7я>", "</ABCDEFGHIJKLMNxЯ>",
       "<abcdefghijklmn", ".я>", "7\\u042f>", "<abcdefghijklmn\xe4\xb8\xadя>"},
      true, true},
+    // variable-width tags: optional letters and groups, an optional class element, '|'
+    {{"think(ing)?", "thoughts?", "t[0-9]?"},
+     {"<think>", "</THINKING>", "<thinking>", "</think>", "<thinki", "ng>", "<think(ing)?>", "<think(ing", "<thoughts>",
+      "</thought>", "<THOUGHT>", "</Thoughts>", "<thought", "s>", "<t>", "</t>", "<t7>", "</T7>", "<t>>", "<t<>", "<té>",
+      "<t\\n>", "<t[0-9]?>", "<t", "7>"},
+     false, false, true},
+    {{"step[0-9]?|phase", "a(b|c.)?d", "abcdefghijklmno?p"},
+     {"<step>", "</STEP4>", "<step4>", "<phase>", "</Phase>", "<step|phase>", "<ste", "p>", "<abd>", "</ACXD>", "<ad>", "<ac>d>",
+      "</ac中d>", "<ac<d>", "<a(b|c.)?d>", "<abcdefghijklmnop>", "</ABCDEFGHIJKLMNP>", "<abcdefghijklmnoq>",
+      "<abcdefghijklmn", "op>", "p>"},
+     false, false, true},
+    {{"réflexions?", "思(考)?", "é[0-9]?"},
+     {"<réflexion>", "</RÉFLEXIONS>", "<R\\u00c9flexions>", "<réflexions?>", "<réflexion", "s>", "<思>", "</思考>", "<思(考)?>",
+      "<\\u601d", "考>", "<é>", "</É7>", "<é>>", "<éé>", "<é", "7>"},
+     true, true, true},
 };
 const ClassSet* g_class = nullptr;  // the class tag set of this iteration (null: the default tags)
 
@@ -173,6 +194,47 @@ bool same(const Run& x, const Run& y) {
          x.fin_texts == y.fin_texts;
 }
 
+// A random string over the alphabet of the tag grammar (and a little beyond it), or one of the
+// shapes a recursive parser can trip over.
+std::string rand_tag() {
+  static const char* kFixed[] = {"(", "a|", "(?", "a(?", "(a", "a)", "((a)", "a(b|", "a??", "a?*", "|", "()", "(?:)", "a(|)b",
+                                 "[", "a[", "a[^", "a[]", "a\\", "?", "a(?:b|c)?(d|e)?(f|g)?(h|i)?(j|k)?"};
+  switch (R(8)) {
+    case 0: return kFixed[R(sizeof(kFixed) / sizeof(kFixed[0]))];
+    case 1: return std::string((size_t)(1 + R(100)), '(') + "a" + std::string((size_t)R(101), ')');
+    case 2: return "a" + std::string((size_t)R(100), '?');
+    default: break;
+  }
+  static const char* kAtoms[] = {"a", "b", "t", "(", ")", "(?:", "|", "?", ".", "[0-9]", "[^a]", "[", "]", "\\.", "\\",
+                                 "*", "+", "{2}", "é", "思", "<", ">", "/", "^", "$", " ", "X"};
+  std::string t;
+  const int n = 1 + R(R(4) == 0 ? 70 : 14);
+  for (int i = 0; i < n; ++i) t += kAtoms[R(sizeof(kAtoms) / sizeof(kAtoms[0]))];
+  return t;
+}
+
+// make_tags over malformed tags: accepted or refused with std::invalid_argument, nothing else.
+// An accepted set runs one small stream, so its tables are walked too.
+bool malformed_tags_hold() {
+  std::vector<std::string> tags;
+  const int n = 1 + R(3);
+  for (int i = 0; i < n; ++i) tags.push_back(rand_tag());
+  const bool unicode = R(2), mixed = R(2), variants = R(4) != 0;
+  try {
+    const Tags t = make_tags(tags, true, unicode, mixed, variants);
+    const auto rows = tagset_rows(tags, true, unicode, mixed, variants);
+    if ((int)rows.size() != t.ts.n || t.ts.n > kMaxTags) return false;
+    std::string text = "<" + tags[0] + "></" + tags[0] + "><";
+    for (const auto& r : rows) text += "<" + r.first + ">x</" + r.first + ">";
+    FilterState fs;
+    std::string out;
+    filter_feed(t, fs, (const uint8_t*)text.data(), text.size(), out);
+    (void)strip_final(t, (const uint8_t*)text.data(), text.size());
+  } catch (const std::invalid_argument&) {
+  }
+  return true;
+}
+
 std::string rand_json(int depth = 0) {
   int k = R(depth > 3 ? 5 : 8);
   switch (k) {
@@ -212,7 +274,8 @@ int main(int argc, char** argv) {
     g_class = it % 2 ? &kClassSets[(it / 2) % (int)(sizeof(kClassSets) / sizeof(kClassSets[0]))] : nullptr;
     const Tags tags = make_tags(g_class ? g_class->tags : default_tags,
                                 g_class != nullptr && (!g_class->unicode || g_class->mixed),
-                                g_class != nullptr && g_class->unicode, g_class != nullptr && g_class->mixed);
+                                g_class != nullptr && g_class->unicode, g_class != nullptr && g_class->mixed,
+                                g_class != nullptr && g_class->variants);
     int ns = 1 + R(4);
     std::vector<std::string> bodies;
     std::vector<bool> filt;
@@ -228,6 +291,9 @@ int main(int argc, char** argv) {
     Run split = run_engine(tags, bodies, filt, true);
     if (!same(whole, split)) {
       if (++fails <= 3) fprintf(stderr, "streaming invariance violated (iteration %d)\n", it);
+    }
+    if (!malformed_tags_hold()) {
+      if (++fails <= 3) fprintf(stderr, "malformed tags: rows and tables disagree (iteration %d)\n", it);
     }
     // strip_final: stripping a stripped text (no tags left in it) only re-strips whitespace
     std::string t = rand_content() + rand_content();

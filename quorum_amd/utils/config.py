@@ -300,6 +300,13 @@ class RuntimeConfig:
                ("réfl.xion", "思[0-9]", "é."): the class rules, the text folded as it is read.  A
                non-ASCII member of a bracket class ("a[é]") is still refused.  Off (the default):
                such a tag list needs the python engine
+    native_variant_tags: with native_regex_tags on (refused otherwise), variable-width tags also
+               run on the native engines: '?' after an element or a group, '|' and groups
+               "(...)" / "(?:...)" — "thoughts?", "think(ing)?", "think|reason".  A tag runs as
+               its fixed-width expansions in the regex's priority order, at most 16 per tag list.
+               "*", "+", "{...}", lazy forms, anchors and shorthands are still refused.  A
+               non-ASCII tag of this form needs native_mixed_tags as well.  Off (the default):
+               such a tag needs the python engine
     """
 
     engine: str = "auto"
@@ -326,6 +333,7 @@ class RuntimeConfig:
     native_regex_tags: bool = False
     native_unicode_tags: bool = False
     native_mixed_tags: bool = False
+    native_variant_tags: bool = False
 
     def __post_init__(self):
         if not isinstance(self.native_regex_tags, bool):
@@ -337,6 +345,10 @@ class RuntimeConfig:
         if self.native_mixed_tags and not (self.native_regex_tags and self.native_unicode_tags):
             raise ValueError("runtime.native_mixed_tags needs runtime.native_regex_tags and "
                              "runtime.native_unicode_tags both true")
+        if not isinstance(self.native_variant_tags, bool):
+            raise ValueError(f"runtime.native_variant_tags must be true or false, got {self.native_variant_tags!r}")
+        if self.native_variant_tags and not self.native_regex_tags:
+            raise ValueError("runtime.native_variant_tags needs runtime.native_regex_tags true")
 
     @classmethod
     def from_config(cls, cfg: Dict[str, Any]) -> "RuntimeConfig":

@@ -76,6 +76,9 @@ def main():
     ap.add_argument("--mixed", action="store_true",
                     help="with --classes and --unicode: class and non-ASCII tags in one set (runtime.native_mixed_tags), "
                          "e.g. --tags think,réflexion,t[0-9] or --tags think,réfl.xion (a mixed tag set: the class kernels)")
+    ap.add_argument("--variants", action="store_true",
+                    help="with --classes: variable-width tags ('?', '|', groups: runtime.native_variant_tags), e.g. "
+                         "--tags 'think(ing)?,thoughts?' or --tags 't[0-9]?' --body-tag t (the class kernels)")
     ap.add_argument("--body-tag", default="think",
                     help="mock shape: the think block's tag as the upstream writes it, e.g. réflexion or RÉFLEXION")
     args = ap.parse_args()
@@ -92,7 +95,7 @@ def main():
         # a class tag set runs on a grid of its own kind (the class kernel)
         # (so does a pair tag set: --unicode and a cased non-ASCII character in a tag)
         grid = ext.HipGrid(0, args.grid, 8, classes=(args.classes or args.unicode)
-                           and ext.tagset_has_classes(tags, args.classes, args.unicode, args.mixed))
+                           and ext.tagset_has_classes(tags, args.classes, args.unicode, args.mixed, args.variants))
     combos = {"ft": (True, True), "f": (True, False), "t": (False, True)}
     for filt, emit in [combos[c] for c in args.combos.split(",")]:
         for n in [int(x) for x in args.slots.split(",")]:
@@ -103,6 +106,8 @@ def main():
                 kw["unicode"] = True
             if args.mixed:
                 kw["mixed"] = True
+            if args.variants:
+                kw["variants"] = True
             eng = NativeEngine(args.engine, tags, device=0, max_slots=4096, content_cap=1 << 16, **kw)
             walls = []
             evs = [e + b"\n\n" for e in body.split(b"\n\n") if e]
