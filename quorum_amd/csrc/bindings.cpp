@@ -25,8 +25,8 @@ namespace {
 struct PyStreamFilter {
   Tags tags;
   FilterState fs;
-  PyStreamFilter(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed, bool variants)
-      : tags(make_tags(t, classes, unicode, mixed, variants)) {}
+  PyStreamFilter(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed, bool variants, bool extended)
+      : tags(make_tags(t, classes, unicode, mixed, variants, extended)) {}
   py::bytes feed(const std::string& s) {
     std::string out;
     filter_feed(tags, fs, (const uint8_t*)s.data(), s.size(), out);
@@ -40,8 +40,8 @@ struct PyStreamFilter {
 
 struct PyStripper {
   Tags tags;
-  PyStripper(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed, bool variants)
-      : tags(make_tags(t, classes, unicode, mixed, variants)) {}
+  PyStripper(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed, bool variants, bool extended)
+      : tags(make_tags(t, classes, unicode, mixed, variants, extended)) {}
   py::bytes strip(const std::string& s) { return py::bytes(strip_final(tags, (const uint8_t*)s.data(), s.size())); }
 };
 
@@ -143,6 +143,7 @@ ServerCfg server_cfg_from(const py::dict& d) {
   gb("tag_unicode", c.tag_unicode);
   gb("tag_mixed", c.tag_mixed);
   gb("tag_variants", c.tag_variants);
+  gb("tag_extended", c.tag_extended);
   gs("aggregator_name", c.aggregator_name); gs("prompt_template", c.prompt_template);
   gs("intermediate_separator", c.intermediate_separator); gs("query_format", c.query_format);
   gs("source_label_format", c.source_label_format); gb("include_original_query", c.include_original_query);
@@ -480,39 +481,39 @@ PYBIND11_MODULE(_qmx, m) {
     return py::bytes(out);
   });
   py::class_<PyStreamFilter>(m, "StreamFilter")
-      .def(py::init<const std::vector<std::string>&, bool, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
-           py::arg("unicode") = false, py::arg("mixed") = false, py::arg("variants") = false)
+      .def(py::init<const std::vector<std::string>&, bool, bool, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
+           py::arg("unicode") = false, py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false)
       .def("feed", &PyStreamFilter::feed)
       .def("flush", &PyStreamFilter::flush);
   py::class_<PyStripper>(m, "Stripper")
-      .def(py::init<const std::vector<std::string>&, bool, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
-           py::arg("unicode") = false, py::arg("mixed") = false, py::arg("variants") = false)
+      .def(py::init<const std::vector<std::string>&, bool, bool, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
+           py::arg("unicode") = false, py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false)
       .def("strip", &PyStripper::strip);
   // is this tag list inside what make_tags runs natively (the one definition of the subset)?
-  m.def("tagset_ok", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants) {
+  m.def("tagset_ok", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
     try {
-      make_tags(tags, classes, unicode, mixed, variants);
+      make_tags(tags, classes, unicode, mixed, variants, extended);
       return true;
     } catch (const std::invalid_argument&) {
       return false;
     }
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false);
   // why make_tags refuses this tag list ("" when it does not): the limit's own message
-  m.def("tagset_error", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants) {
+  m.def("tagset_error", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
     try {
-      make_tags(tags, classes, unicode, mixed, variants);
+      make_tags(tags, classes, unicode, mixed, variants, extended);
       return std::string();
     } catch (const std::invalid_argument& e) {
       return std::string(e.what());
     }
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false);
   // distinct tags of the set make_tags builds ("É" and "é" are one)
-  m.def("tagset_size", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants) {
-    return make_tags(tags, classes, unicode, mixed, variants).ts.n;
+  m.def("tagset_size", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
+    return make_tags(tags, classes, unicode, mixed, variants, extended).ts.n;
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false);
   // the case rule of one non-ASCII tag character (qmx_unicode_fold.h): (kind, partner) with
   // kind 0 uncased, 1 a simple case pair, 2 refused; partner: the pair's other member, else cp
   m.def("unicode_tag_char", [](uint32_t cp) {
@@ -521,21 +522,21 @@ PYBIND11_MODULE(_qmx, m) {
     return py::make_tuple(kind, kind == 1 ? unicode_tag_partner(cp) : cp);
   });
   // the kind of the tag set this list makes (qmx_text.h TagKind)
-  m.def("tagset_kind", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants) {
-    const TagKind k = make_tags(tags, classes, unicode, mixed, variants).kind;
+  m.def("tagset_kind", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
+    const TagKind k = make_tags(tags, classes, unicode, mixed, variants, extended).kind;
     return k == TAGS_MIXED ? "mixed" : k == TAGS_PAIR ? "pair" : k == TAGS_CLASS ? "class" : "literal";
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false);
   // of the class kind (class, pair or mixed)?  Such a tag set's engines need HipGrid(classes=True)
-  m.def("tagset_has_classes", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants) {
-    return make_tags(tags, classes, unicode, mixed, variants).kind != TAGS_LITERAL;
+  m.def("tagset_has_classes", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
+    return make_tags(tags, classes, unicode, mixed, variants, extended).kind != TAGS_LITERAL;
   }, py::arg("tags"), py::arg("classes") = true, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false);
   // candidates '<' of `text` the GPU kernels would hand to the host path (qmx_text.h
   // class_candidate, the shared suspect rule), with the streaming or the strip tables
   m.def("class_suspects", [](const std::vector<std::string>& tags, const std::string& text, bool strip, bool unicode,
-                             bool mixed, bool variants) {
-    const Tags t = make_tags(tags, true, unicode, mixed, variants);
+                             bool mixed, bool variants, bool extended) {
+    const Tags t = make_tags(tags, true, unicode, mixed, variants, extended);
     int k = 0;
     if (t.kind == TAGS_LITERAL) return k;
     const uint8_t* x = (const uint8_t*)text.data();
@@ -548,24 +549,24 @@ PYBIND11_MODULE(_qmx, m) {
     }
     return k;
   }, py::arg("tags"), py::arg("text"), py::arg("strip") = false, py::arg("unicode") = false, py::arg("mixed") = false,
-     py::arg("variants") = false);
+     py::arg("variants") = false, py::arg("extended") = false);
   // the rows of the set make_tags builds: (row text, index of its tag in `tags`), in order — a
   // variable-width tag (`variants`) has one row per fixed-width expansion, every other tag one
-  m.def("tagset_rows", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants) {
+  m.def("tagset_rows", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
     py::list out;
-    for (const auto& r : tagset_rows(tags, classes, unicode, mixed, variants))
+    for (const auto& r : tagset_rows(tags, classes, unicode, mixed, variants, extended))
       out.append(py::make_tuple(py::bytes(r.first).attr("decode")("utf-8"), r.second));
     return out;
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false, py::arg("mixed") = false,
-     py::arg("variants") = false);
+     py::arg("variants") = false, py::arg("extended") = false);
   env_refresh();
   py::class_<CpuEngine> ce(m, "CpuEngine");
-  ce.def(py::init([](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants) {
+  ce.def(py::init([](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
            env_refresh();
-           return new CpuEngine(make_tags(tags, classes, unicode, mixed, variants));
+           return new CpuEngine(make_tags(tags, classes, unicode, mixed, variants, extended));
          }),
          py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false);
   bind_engine(ce);
   // the multi-door grid of loop ticks (tests drive several door engines from Python threads)
   py::class_<HipGrid>(m, "HipGrid")
@@ -611,15 +612,15 @@ PYBIND11_MODULE(_qmx, m) {
   py::class_<HipEngine> he(m, "HipEngine");
   he.def(py::init([](const std::vector<std::string>& tags, int device, int tile, int max_slots, int content_cap,
                       int lanes, HipGrid* grid, int door, int ndoors, bool classes, bool unicode, bool mixed,
-                      bool variants) {
+                      bool variants, bool extended) {
            env_refresh();
-           return new HipEngine(make_tags(tags, classes, unicode, mixed, variants), device, tile, max_slots, content_cap, lanes, grid,
+           return new HipEngine(make_tags(tags, classes, unicode, mixed, variants, extended), device, tile, max_slots, content_cap, lanes, grid,
                                 door, ndoors);
          }),
          py::arg("tags"), py::arg("device"), py::arg("tile_bytes") = 16384, py::arg("max_slots") = 8192,
          py::arg("content_cap") = 1 << 20, py::arg("lanes") = 1, py::arg("grid") = nullptr, py::arg("door") = -1,
          py::arg("ndoors") = 1, py::arg("classes") = false, py::arg("unicode") = false, py::arg("mixed") = false,
-         py::arg("variants") = false, py::keep_alive<1, 8>());
+         py::arg("variants") = false, py::arg("extended") = false, py::keep_alive<1, 8>());
   bind_engine(he);
   he.def("kernel_stats", &HipEngine::kernel_stats);
   he.def("debug_poison_results", &HipEngine::debug_poison_results, py::arg("ahead") = 1);

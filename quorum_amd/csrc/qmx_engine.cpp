@@ -30,6 +30,27 @@ struct Elem {
 
 bool printable(uint8_t c) { return c >= 0x20 && c < 0x7f; }
 
+// A refusal with a message of its own, thrown inside the tag parsers (build_tags adds the tag).
+struct TagRefusal {
+  const char* msg;
+};
+const char* kUpperShorthand =
+    "tag holds \\D, \\W or \\S: the reference's streaming filter compiles the lowercased tag (\\d, \\w, \\s) and its "
+    "final strip the tag as written, so the two disagree (runs with --impl python): ";
+const char* kEmptyRepeat = "tag repeats a group that can match the empty string (runs with --impl python): ";
+
+// The shorthand at t[i] == '\\' (make_tags' `extended`): its ASCII table is or-ed into tab and its
+// flag bit returned; 0: no shorthand there.  \D, \W and \S are refused with their own message.
+uint8_t shorthand_at(const std::string& t, size_t i, uint32_t* tab) {
+  if (i + 1 >= t.size()) return 0;
+  const char c = t[i + 1];
+  if (c == 'D' || c == 'W' || c == 'S') throw TagRefusal{kUpperShorthand};
+  const uint32_t* a = c == 'd' ? kDigitAscii : c == 'w' ? kWordAscii : c == 's' ? kSpaceAscii : nullptr;
+  if (!a) return 0;
+  for (int k = 0; k < 4; ++k) tab[k] |= a[k];
+  return c == 'd' ? CLS_SH_DIGIT : c == 'w' ? CLS_SH_WORD : CLS_SH_SPACE;
+}
+
 void tab_set(uint32_t* tab, uint8_t c) {  // under IGNORECASE: both cases of a letter
   for (uint8_t v : {c, lower_ascii(c), (uint8_t)((c >= 'a' && c <= 'z') ? c - 32 : c)}) tab[v >> 5] |= 1u << (v & 31);
 }
@@ -37,12 +58,14 @@ void tab_set(uint32_t* tab, uint8_t c) {  // under IGNORECASE: both cases of a l
 // "[...]" at t[i] == '[': members are printable ASCII literals other than "<>/[", ranges and
 // the escapes \\ \] \^ \- \[.  False for everything Python's parser reads differently or
 // warns about (a leading ']', "--", "&&", "~~", "||", shorthands, POSIX classes).
-bool parse_bracket(const std::string& t, size_t& i, Elem& e) {
+// extended: \d, \w and \s are members too (never a range endpoint: an error in re).
+bool parse_bracket(const std::string& t, size_t& i, Elem& e, bool extended) {
   size_t j = i + 1;
   bool neg = false;
   if (j < t.size() && t[j] == '^') { neg = true; ++j; }
   if (j < t.size() && t[j] == ']') return false;
   uint32_t tab[4] = {0, 0, 0, 0};
+  uint8_t sh = 0;
   // one member byte at t[j] (escapes resolved); '-' is handled by the caller
   auto member = [&](uint8_t* out) {
     if (j >= t.size()) return false;
@@ -69,6 +92,15 @@ bool parse_bracket(const std::string& t, size_t& i, Elem& e) {
       ++j;
       continue;
     }
+    if (extended && t[j] == '\\') {
+      const uint8_t f = shorthand_at(t, j, tab);
+      if (f) {
+        sh |= f;
+        j += 2;
+        if (j + 1 < t.size() && t[j] == '-' && t[j + 1] != ']') return false;
+        continue;
+      }
+    }
     uint8_t lo;
     if (!member(&lo)) return false;
     if (j + 1 < t.size() && t[j] == '-' && t[j + 1] != ']') {  // range lo-hi
@@ -83,7 +115,7 @@ bool parse_bracket(const std::string& t, size_t& i, Elem& e) {
   }
   i = j + 1;
   e.cls = true;
-  e.flags = neg ? CLS_WIDE : 0;
+  e.flags = (neg ? CLS_WIDE : 0) | sh;
   for (int k = 0; k < 4; ++k) e.tab[k] = neg ? ~tab[k] : tab[k];
   return true;
 }
@@ -92,10 +124,13 @@ bool parse_bracket(const std::string& t, size_t& i, Elem& e) {
 // it lies outside the class subset.  wide: a byte >= 0x80 outside a bracket class is a literal
 // element of its own (a mixed tag set: the bytes of a non-ASCII literal character, already
 // lowered through the pair table).
-bool parse_elem(const std::string& t, size_t& i, Elem& e, bool wide) {
+bool parse_elem(const std::string& t, size_t& i, Elem& e, bool wide, bool extended = false) {
   const uint8_t c = (uint8_t)t[i];
   const size_t i0 = i;
-  if (c == '\\') {
+  if (c == '\\' && extended && (e.flags = shorthand_at(t, i, e.tab)) != 0) {
+    e.cls = true;  // a shorthand on its own: a class of one member
+    i += 2;
+  } else if (c == '\\') {
     if (i + 1 >= t.size() || !std::strchr(".^$*+?{}[]\\|()-", t[i + 1])) return false;
     e.lit = (uint8_t)t[i + 1];
     i += 2;
@@ -105,7 +140,7 @@ bool parse_elem(const std::string& t, size_t& i, Elem& e, bool wide) {
     for (int k = 0; k < 4; ++k) e.tab[k] = ~0u;
     ++i;
   } else if (c == '[') {
-    if (!parse_bracket(t, i, e)) return false;
+    if (!parse_bracket(t, i, e, extended)) return false;
   } else if (wide && c >= 0x80) {
     e.lit = c;
     ++i;
@@ -135,6 +170,8 @@ bool parse_class_tag(const std::string& t, std::vector<Elem>& out, bool wide = f
 // first), concatenation distributes over ordered alternation and keeps the priority order, and
 // a backtracking matcher returns the first success in that order.  A recursive-descent parser
 // over alt := seq ('|' seq)*, seq := (atom '?'?)*, atom := element | group.
+// With `extended` an element may be a shorthand (\d, \w, \s, alone or in a bracket class) and an
+// atom may carry a count instead of the '?': "{m}", "{m,n}" or "{,n}" (VariantParser::counted).
 typedef std::vector<Elem> Row;
 typedef std::vector<Row> Rows;  // in priority order, no two equal
 
@@ -150,6 +187,16 @@ bool same_row(const Row& a, const Row& b) {
 }
 
 struct TooManyRows {};
+struct RowTooLong {};  // a row of more than kMaxTagLen elements: no such row fits "</" + match + ">" in 64 bytes
+
+// l followed by r.  Nested counts multiply the elements of one row ("((a{61}){61}){61}"), so the
+// length is bounded here, where a row grows, and not after the expansion.
+Row join_rows(const Row& l, const Row& r) {
+  if (l.size() + r.size() > (size_t)kMaxTagLen) throw RowTooLong();
+  Row c = l;
+  c.insert(c.end(), r.begin(), r.end());
+  return c;
+}
 
 // A later duplicate of a row never matches where the first did not: dropped.  The count of
 // distinct rows only grows towards the whole tag, so more than kMaxTags here is more at the end.
@@ -163,6 +210,7 @@ void add_row(Rows& rows, const Row& r) {
 struct VariantParser {
   const std::string& t;
   bool wide;
+  bool extended;  // shorthands, and counted repetition after an atom
   size_t i = 0;
   bool ops = false;  // a '?', a '|' or a group was read: a variable-width tag
 
@@ -192,10 +240,12 @@ struct VariantParser {
         ++i;
       } else {
         Elem e;
-        if (!parse_elem(t, i, e, wide)) return false;
+        if (!parse_elem(t, i, e, wide, extended)) return false;
         a.assign(1, Row(1, e));
       }
-      if (i < t.size() && t[i] == '?') {  // greedy: present, then absent; "??", "?+", "?*", "?{" are refused
+      if (extended && i < t.size() && t[i] == '{') {
+        if (!counted(a)) return false;
+      } else if (i < t.size() && t[i] == '?') {  // greedy: present, then absent; "??", "?+", "?*", "?{" are refused
         ops = true;
         ++i;
         if (i < t.size() && std::strchr("?+*{", t[i])) return false;
@@ -203,38 +253,79 @@ struct VariantParser {
       }
       Rows next;
       for (const Row& l : out)
-        for (const Row& r : a) {
-          Row c = l;
-          c.insert(c.end(), r.begin(), r.end());
-          add_row(next, c);
-        }
+        for (const Row& r : a) add_row(next, join_rows(l, r));
       out.swap(next);
     }
+    return true;
+  }
+  // "{m}", "{m,n}" or "{,n}" at t[i] == '{' after the atom whose rows are `a` (m <= n <= 61):
+  // x{m,n} is m copies of x and n - m nested greedy optionals, x...x(?:x(?:x)?)?, so the rows and
+  // their order come from add_row as for '?'.  False for "{m,}", m > n, a quantifier after the
+  // '}' and every form re reads as a literal brace ("{", "{x}", "{ 1}", "{}", "{,}").
+  static Rows cat(const Rows& l, const Rows& r) {
+    Rows out;
+    for (const Row& x : l)
+      for (const Row& y : r) add_row(out, join_rows(x, y));
+    return out;
+  }
+  bool counted(Rows& a) {
+    size_t j = i + 1;
+    auto number = [&](int* v) {  // up to three digits ("061" is 61, the largest count); a longer run is refused
+      const size_t j0 = j;
+      *v = 0;
+      while (j < t.size() && t[j] >= '0' && t[j] <= '9' && j - j0 < 3) *v = *v * 10 + (t[j++] - '0');
+      return j > j0;
+    };
+    int m = 0, n = 0;
+    const bool has_m = number(&m);
+    if (j < t.size() && t[j] == ',') {
+      ++j;
+      if (!number(&n)) return false;  // "{m,}" is unbounded, "{,}" a literal
+    } else {
+      if (!has_m) return false;
+      n = m;
+    }
+    if (j >= t.size() || t[j] != '}' || m > n || n > kMaxTagLen) return false;
+    ++j;
+    if (j < t.size() && std::strchr("?+*{", t[j])) return false;
+    for (const Row& r : a)
+      if (r.empty()) throw TagRefusal{kEmptyRepeat};  // (re's empty-iteration guard is not the row identity)
+    i = j;
+    ops = true;
+    Rows opt(1, Row());  // the n - m nested optionals, innermost first
+    for (int k = 0; k < n - m; ++k) {
+      opt = cat(a, opt);
+      add_row(opt, Row());
+    }
+    Rows out(1, Row());
+    for (int k = 0; k < m; ++k) out = cat(out, a);
+    a = cat(out, opt);
     return true;
   }
 };
 
 // The rows of one tag; *ops: it is a variable-width tag.  False outside the subset.
-bool parse_variant_tag(const std::string& t, Rows& out, bool wide, bool* ops) {
-  VariantParser p{t, wide};
+bool parse_variant_tag(const std::string& t, Rows& out, bool wide, bool extended, bool* ops) {
+  VariantParser p{t, wide, extended};
   if (!p.alt(out, 0) || p.i != t.size()) return false;
   *ops = p.ops;
   return true;
 }
 
 Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants,
-                std::vector<std::pair<std::string, int>>* rows_out);
+                bool extended, std::vector<std::pair<std::string, int>>* rows_out);
 
 }  // namespace
 
-Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants) {
-  return build_tags(tags, classes, unicode, mixed, variants, nullptr);
+Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants,
+               bool extended) {
+  return build_tags(tags, classes, unicode, mixed, variants, extended, nullptr);
 }
 
 std::vector<std::pair<std::string, int>> tagset_rows(const std::vector<std::string>& tags, bool classes, bool unicode,
-                                                     bool mixed, bool variants) {
+                                                     bool mixed, bool variants, bool extended) {
   std::vector<std::pair<std::string, int>> rows;
-  build_tags(tags, classes, unicode, mixed, variants, &rows);
+  build_tags(tags, classes, unicode, mixed, variants, extended, &rows);
   return rows;
 }
 
@@ -266,9 +357,10 @@ uint32_t unicode_tag_partner(uint32_t cp) {
 
 namespace {
 Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants,
-                std::vector<std::pair<std::string, int>>* rows_out) {
+                bool extended, std::vector<std::pair<std::string, int>>* rows_out) {
   mixed = mixed && classes && unicode;
   variants = variants && classes;
+  extended = extended && variants;
   Tags out;
   std::memset(&out, 0, sizeof(out));
   TagSet& ts = out.ts;
@@ -355,11 +447,17 @@ Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode
         const bool w = wide && unicode;
         rows.clear();
         try {
-          ok = parse_variant_tag(w ? tw : t0, rows, w, &var);
+          ok = parse_variant_tag(w ? tw : t0, rows, w, extended, &var);
         } catch (const TooManyRows&) {
           throw std::invalid_argument("thinking tags expand to more than 16 rows: " + t0);
+        } catch (const RowTooLong&) {
+          throw std::invalid_argument("unsupported tag length: " + t0);
+        } catch (const TagRefusal& r) {
+          throw std::invalid_argument(r.msg + t0);
         }
-        if (ok && !var) ok = (mix || !wide) && !rows[0].empty() && !rows[0][0].cls;
+        // (a shorthand in front gets the class-first message of the rows below)
+        if (ok && !var)
+          ok = (mix || !wide) && !rows[0].empty() && (!rows[0][0].cls || (rows[0][0].flags & CLS_SH));
       } else if (ok) {
         ok = parse_class_tag(mix ? tw : t0, rows[0], mix);
       }
@@ -368,7 +466,7 @@ Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode
         if (elems.empty()) throw std::invalid_argument("tag has an empty alternative: " + t0);
         if (elems[0].cls) throw std::invalid_argument("tag has an alternative that begins with a class: " + t0);
         int bound = 3;  // bytes of the longest "</" + match + ">"
-        for (const Elem& e : elems) bound += (e.flags & CLS_WIDE) ? 4 : 1;
+        for (const Elem& e : elems) bound += (e.flags & (CLS_WIDE | CLS_SH)) ? 4 : 1;
         if (bound > kMaxTail) throw std::invalid_argument("unsupported tag length: " + t0);
       }
     }
@@ -449,6 +547,7 @@ Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode
     std::memset(tc.clsmask, 0, sizeof(tc.clsmask));  // (the tables of the other kinds are what they were)
     tc.walk = 0;
   }
+  if (extended && out.kind == TAGS_CLASS) tc.var |= kVarExtended;
   // (a literal tag set keeps no tables: its source text is its names)
   if (out.kind == TAGS_LITERAL) std::memset(&tc, 0, sizeof(tc));
   return out;

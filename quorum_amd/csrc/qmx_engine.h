@@ -46,12 +46,17 @@ struct Tags {
 // the regex's priority order (`think(ing)?`: thinking, think), one entry of the set each (at
 // most 16 per set), all with the tag's own source text (TagClasses::var); the set is of the
 // class kind, or of the mixed kind when it holds a non-ASCII character (which needs `mixed`)
+// extended: with variants, also accept the shorthands \d, \w and \s (an element of their own or
+// members of a bracket class; a class with one holds some code points >= 0x80, which the host
+// walks look up in qmx_unicode_classes.h and the kernels leave to the host) and counted
+// repetition {m}, {m,n}, {,n} after an element or a group, which expands into rows as '?' does
 Tags make_tags(const std::vector<std::string>& tags, bool classes = false, bool unicode = false, bool mixed = false,
-               bool variants = false);
+               bool variants = false, bool extended = false);
 // The rows of the set make_tags builds, in order, as text (a class position as "." or "[]"),
 // each with the index of its tag in `tags` (tests, tools/kbench.py)
 std::vector<std::pair<std::string, int>> tagset_rows(const std::vector<std::string>& tags, bool classes = false,
-                                                     bool unicode = false, bool mixed = false, bool variants = false);
+                                                     bool unicode = false, bool mixed = false, bool variants = false,
+                                                     bool extended = false);
 // the case rule of a non-ASCII tag character: 0 uncased, 1 a pair (*lower: its lower member), 2 refused
 int unicode_tag_char(uint32_t cp, uint32_t* lower);
 uint32_t unicode_tag_partner(uint32_t cp);  // the other member of cp's pair (cp: none)

@@ -506,7 +506,8 @@ __device__ __noinline__ int mixed_hold_dev(const uint8_t* x, int q, int e, const
     const bool pre = mixed_source_prefix(x, q, e, *ts, *tc);
     return (pre ? 1 : 0) | (tk > 0 && !pre ? 2 : 0);
   }
-  return mixed_prefix(x, q, e, *ts, *tc) ? 1 : 0;
+  const int r = mixed_prefix(x, q, e, *ts, *tc);
+  return r == kWalkHost ? 2 : r;  // (a byte >= 0x80 at a class with a shorthand: the host decides the tile)
 }
 // the first in list order of the fast matchers' token and the walk's
 __device__ __forceinline__ int mixed_first(int lit, int tok) {
@@ -528,7 +529,9 @@ __device__ __forceinline__ int class_token(const uint8_t* Z, int Zn, int p, cons
 // (tk: the token that completes later in Z, 0: none; dq: the depth before it).  Outside a
 // block the reference holds what is a prefix of a tag's SOURCE text, so an open tag whose
 // first part was released at this cut is no token at all: bit 1, the tile goes to the host.
-// Inside a block: a proper class-aware prefix of any pattern.  Bit 0: hold.
+// Inside a block: a proper class-aware prefix of any pattern — or, where the walk meets a byte
+// >= 0x80 at a class with a shorthand (kWalkHost), bit 1 again: never "no prefix", which would
+// release held text.  Bit 0: hold.
 __device__ __forceinline__ int class_hold(const uint8_t* Z, int q, int e, const KParams& P, int dq, int tk) {
   if (e - q > kMaxTail) return 0;
   if (is_pair_set(*P.cls)) return fold_prefix_dev(Z, q, e, &P.ts, P.cls, dq == 0);
@@ -537,7 +540,8 @@ __device__ __forceinline__ int class_hold(const uint8_t* Z, int q, int e, const 
     const bool pre = source_prefix(Z, q, e, P.ts, *P.cls);
     return (pre ? 1 : 0) | (tk > 0 && !pre ? 2 : 0);
   }
-  return class_prefix(Z, q, e, P.ts, *P.cls) ? 1 : 0;
+  const int r = class_prefix(Z, q, e, P.ts, *P.cls);
+  return r == kWalkHost ? 2 : r;  // (a byte >= 0x80 at a class with a shorthand: the host decides the tile)
 }
 
 // holdback test at stream position e (Z coords): returns cut (q when held, else e).
@@ -2737,7 +2741,8 @@ __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n
               const bool ne = lane < nl && cmp &&
                               lower_ascii(src[ppos + 1 + lane]) != lower_ascii(src[cpos + 2 + lane]);
               if (__ballot(ne) != 0) {
-                if (__builtin_expect(is_mixed_set(*tc), 0)) {  // not this open's close: on to the tag's next one
+                // (a class set made with the extended language as well: kVarExtended)
+                if (__builtin_expect(is_mixed_set(*tc) || (tc->var & kVarExtended) != 0, 0)) {  // not this open's close: on to the tag's next one
                   cur = cpos + 1;         // (none left: the open stays pending, the host path decides)
                   continue;
                 }

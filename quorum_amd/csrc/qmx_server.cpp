@@ -3702,7 +3702,8 @@ int run_server(const ServerCfg& cfg0) {
   g_drain.store(false);
   g_ready.store(0);
   // the one tag set of this server: every engine, the verify shadows and the loops share it
-  const Tags tags = make_tags(cfg.tags, cfg.tag_classes, cfg.tag_unicode, cfg.tag_mixed, cfg.tag_variants);
+  const Tags tags = make_tags(cfg.tags, cfg.tag_classes, cfg.tag_unicode, cfg.tag_mixed, cfg.tag_variants,
+                              cfg.tag_extended);
   std::vector<std::unique_ptr<Loop>> loops;
   std::vector<std::thread> ts;
   for (int i = 0; i < std::max(1, cfg.threads); ++i) loops.emplace_back(new Loop(cfg, i, tags));

@@ -62,6 +62,7 @@ struct ServerCfg {
   bool tag_unicode = false;  // runtime.native_unicode_tags: non-ASCII tags (uncased / simple case pairs) run natively
   bool tag_mixed = false;    // runtime.native_mixed_tags: with both, class and non-ASCII tags in one set and one tag
   bool tag_variants = false;  // runtime.native_variant_tags: with tag_classes, tags with '?', '|' and groups run natively
+  bool tag_extended = false;  // runtime.native_extended_tags: with tag_variants, the shorthands d, w, s and counted repetition run natively
   // strategy.aggregate (consulted whatever strategy is selected, as in quorum)
   std::string aggregator_name;  // empty = none
   std::string prompt_template, intermediate_separator, query_format, source_label_format;

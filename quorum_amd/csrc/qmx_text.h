@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qmx_unicode_classes.h"
+
 #define QMX_HD __host__ __device__ inline
 
 namespace qmx {
@@ -50,6 +52,11 @@ enum TagKind : int { TAGS_LITERAL, TAGS_CLASS, TAGS_PAIR, TAGS_MIXED };
 constexpr int kMaxClasses = 32;
 constexpr int kMaxFold = 32;  // distinct pair characters of a pair tag set
 enum : uint8_t { CLS_WIDE = 1, CLS_DOT = 2 };  // accepts non-ASCII code points / is a '.'
+// A class with a shorthand (make_tags(..., extended = true): \d, \w, \s, alone or in brackets) holds
+// SOME code points >= 0x80: one bit per shorthand, tables in qmx_unicode_classes.h (host only).
+// With such a bit CLS_WIDE says the class is negated: the answer is member XOR negated.  Read
+// only where a class position holds a byte >= 0x80.
+enum : uint8_t { CLS_SH_DIGIT = 4, CLS_SH_WORD = 8, CLS_SH_SPACE = 16, CLS_SH = 4 | 8 | 16 };
 struct TagClasses {
   int n;                               // distinct class definitions
   uint32_t tab[kMaxClasses][4];        // ASCII acceptance under IGNORECASE | DOTALL (bit b of the 128)
@@ -80,8 +87,12 @@ struct TagClasses {
   // TagSet each, src[] of every one the tag's whole source text.  var: bit r — row r comes from
   // such a tag; 0 for every other set.  The last field, read only where a class position holds
   // '<', '>' or a byte >= 0x80 (variant_mismatch): the other sets' data and loads are what they were.
+  // Bits 0-15 are rows.  kVarExtended (make_tags(..., extended = true)): the set was made with
+  // the extended language; the finalize of such a class set goes on to a tag's next close where
+  // the first is not the open's captured text (`step\d`: <step1>a</step2>b</step1>).
   uint32_t var;
 };
+constexpr uint32_t kVarRows = 0xffffu, kVarExtended = 1u << 31;
 // The kernels of the class kind run class, pair and mixed tag sets (KParams::cls is set for all
 // three): which of them the tables are.
 QMX_HD bool is_pair_set(const TagClasses& tc) { return tc.nfold > 0; }
@@ -158,9 +169,43 @@ QMX_HD bool class_accepts(const TagClasses& tc, int k, uint8_t c, bool strip) {
   return (tc.tab[k][c >> 5] >> (c & 31)) & 1u;
 }
 
+// The character at x[s] (a byte >= 0x80, `ln` bytes by its lead byte) at a position of a class with
+// a shorthand.  1: accepted, 0: not, -1: cut short at n (a proper prefix, whatever it would have been),
+// kWalkHost: a class with a shorthand on the device — the tables of \d, \w and \s are host
+// data (qmx_unicode_classes.h), so the host decides.
+constexpr int kWalkHost = -2;
+inline bool shorthand_holds(uint8_t flags, uint32_t cp) {  // (a host function: the tables are host data)
+  auto in = [cp](const uint32_t (*r)[2], int n) {
+    int lo = 0, hi = n;  // first range whose last member is >= cp
+    while (lo < hi) {
+      const int m = (lo + hi) >> 1;
+      if (r[m][1] < cp) lo = m + 1;
+      else hi = m;
+    }
+    return lo < n && r[lo][0] <= cp;
+  };
+  return ((flags & CLS_SH_DIGIT) && in(kDigitRanges, kDigitRangeCount)) ||
+         ((flags & CLS_SH_WORD) && in(kWordRanges, kWordRangeCount)) ||
+         ((flags & CLS_SH_SPACE) && in(kSpaceRanges, kSpaceRangeCount));
+}
+template <class R>
+QMX_HD int shorthand_char_at(const R& x, int n, int s, uint8_t f, int ln) {  // f: the class's flags, a shorthand bit among them
+#ifdef __HIP_DEVICE_COMPILE__
+  return kWalkHost;
+#else
+  if (s + ln > n) return -1;
+  uint32_t cp = 0xFFFFFFFFu;  // (a stray continuation byte: no member)
+  if (ln == 2) cp = ((x[s] & 0x1Fu) << 6) | (x[s + 1] & 0x3Fu);
+  else if (ln == 3) cp = ((x[s] & 0x0Fu) << 12) | ((x[s + 1] & 0x3Fu) << 6) | (x[s + 2] & 0x3Fu);
+  else if (ln == 4) cp = ((x[s] & 0x07u) << 18) | ((x[s + 1] & 0x3Fu) << 12) | ((x[s + 2] & 0x3Fu) << 6) | (x[s + 3] & 0x3Fu);
+  return shorthand_holds(f, cp) != ((f & CLS_WIDE) != 0) ? 1 : 0;
+#endif
+}
+
 // Walk pattern `pat` (pat < n: "<t>", else "</t>") over x[p:n).  1: it matches, *end is the
 // index after its '>';  0: mismatch;  -1: every byte of x[p:n) matched and the text ended
-// before the pattern did (a proper prefix — a code point cut short at n counts as one).
+// before the pattern did (a proper prefix — a code point cut short at n counts as one);
+// kWalkHost: device code met a byte >= 0x80 at a class with a shorthand (shorthand_char_at).
 template <class R>
 QMX_HD int class_walk(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, int pat, bool strip,
                       int* end) {
@@ -185,8 +230,13 @@ QMX_HD int class_walk(const R& x, int n, int p, const TagSet& ts, const TagClass
       if (!class_accepts(tc, e - 0x80, c, strip)) return 0;
       ++s;
     } else {
-      if (!(tc.flags[e - 0x80] & CLS_WIDE)) return 0;
+      const uint8_t f = tc.flags[e - 0x80];
+      if (!(f & (CLS_WIDE | CLS_SH))) return 0;
       const int ln = c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : c >= 0xC0 ? 2 : 1;
+      if (f & CLS_SH) {
+        const int r = shorthand_char_at(x, n, s, f, ln);
+        if (r != 1) return r;
+      }
       if (s + ln > n) return -1;
       s += ln;
     }
@@ -230,9 +280,10 @@ QMX_HD int class_match_at(const R& x, int n, int p, const TagSet& ts, const TagC
 // class accepts stays suspect.
 enum : int { CC_NONE = 0, CC_MATCH = 1, CC_SUSPECT = 2 };
 // c: '<', '>' or >= 0x80 at a position of class k — a mismatch (not a suspect) of the row?
+// (A class with a shorthand holds some code points >= 0x80 — which, only the host knows: suspect.)
 QMX_HD bool variant_mismatch(const TagClasses& tc, int k, uint8_t c) {
-  if (tc.var == 0) return false;
-  return c >= 0x80 ? !(tc.flags[k] & CLS_WIDE) : !((tc.tab[k][c >> 5] >> (c & 31)) & 1u);
+  if ((tc.var & kVarRows) == 0) return false;
+  return c >= 0x80 ? !(tc.flags[k] & (CLS_WIDE | CLS_SH)) : !((tc.tab[k][c >> 5] >> (c & 31)) & 1u);
 }
 template <class R>
 QMX_HD int class_candidate(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, bool strip, int* tok,
@@ -268,13 +319,17 @@ QMX_HD int class_candidate(const R& x, int n, int p, const TagSet& ts, const Tag
 }
 
 // Is x[q:n) a proper class-aware prefix of some open or close pattern (streaming tables)?
+// 1: yes, 0: no, kWalkHost: some walk could not tell on the device (never on the host).
 template <class R>
-QMX_HD bool class_prefix(const R& x, int q, int n, const TagSet& ts, const TagClasses& tc) {
+QMX_HD int class_prefix(const R& x, int q, int n, const TagSet& ts, const TagClasses& tc) {
+  int res = 0;
   for (int pat = 0; pat < 2 * ts.n; ++pat) {
     int end = 0;
-    if (class_walk(x, n, q, ts, tc, pat, false, &end) == -1) return true;
+    const int r = class_walk(x, n, q, ts, tc, pat, false, &end);
+    if (r == -1) return 1;  // (held: the next tile's candidate meets what a later pattern could not tell)
+    if (r == kWalkHost) res = kWalkHost;
   }
-  return false;
+  return res;
 }
 
 // Is x[q:n), ASCII-lowercased, a prefix of the source text "<" + tag + ">" of some tag?  The
@@ -409,8 +464,13 @@ QMX_HD int mixed_walk(const R& x, int n, int p, const TagSet& ts, const TagClass
         if (!class_accepts(tc, k, c, strip)) return 0;
         ++s;
       } else {
-        if (!(tc.flags[k] & CLS_WIDE)) return 0;
+        const uint8_t f = tc.flags[k];
+        if (!(f & (CLS_WIDE | CLS_SH))) return 0;
         const int ln = utf8_lead_len(c);
+        if (f & CLS_SH) {
+          const int r = shorthand_char_at(x, n, s, f, ln);
+          if (r != 1) return r;
+        }
         if (s + ln > n) return -1;
         s += ln;
       }
@@ -503,12 +563,15 @@ QMX_HD int mixed_candidate(const R& x, int n, int p, const TagSet& ts, const Tag
 
 // class_prefix for a mixed tag set
 template <class R>
-QMX_HD bool mixed_prefix(const R& x, int q, int n, const TagSet& ts, const TagClasses& tc) {
+QMX_HD int mixed_prefix(const R& x, int q, int n, const TagSet& ts, const TagClasses& tc) {
+  int res = 0;
   for (int pat = 0; pat < 2 * ts.n; ++pat) {
     int end = 0;
-    if (mixed_walk(x, n, q, ts, tc, pat, false, &end) == -1) return true;
+    const int r = mixed_walk(x, n, q, ts, tc, pat, false, &end);
+    if (r == -1) return 1;
+    if (r == kWalkHost) res = kWalkHost;
   }
-  return false;
+  return res;
 }
 
 // source_prefix for a mixed tag set: x[q:n), folded, a prefix of "<" + tag source + ">".  A
@@ -555,8 +618,8 @@ QMX_HD int token_at(TagKind kind, const R& x, int n, int p, const TagSet& ts, co
 // tags' source text outside a block and a proper prefix of a pattern inside one.
 template <class R>
 QMX_HD bool held_at(TagKind kind, const R& x, int q, int n, const TagSet& ts, const TagClasses& tc, int depth) {
-  if (kind == TAGS_CLASS) return depth == 0 ? source_prefix(x, q, n, ts, tc) : class_prefix(x, q, n, ts, tc);
-  if (kind == TAGS_MIXED) return depth == 0 ? mixed_source_prefix(x, q, n, ts, tc) : mixed_prefix(x, q, n, ts, tc);
+  if (kind == TAGS_CLASS) return depth == 0 ? source_prefix(x, q, n, ts, tc) : class_prefix(x, q, n, ts, tc) == 1;
+  if (kind == TAGS_MIXED) return depth == 0 ? mixed_source_prefix(x, q, n, ts, tc) : mixed_prefix(x, q, n, ts, tc) == 1;
   return kind == TAGS_PAIR ? fold_pattern_prefix(x, q, n, ts, tc, depth == 0) : pattern_prefix(x, q, n, ts, depth == 0);
 }
 

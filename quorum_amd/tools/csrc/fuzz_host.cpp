@@ -49,6 +49,7 @@ struct ClassSet {
   bool unicode = false;  // a non-ASCII tag set (make_tags' `unicode`), no class tags
   bool mixed = false;    // a mixed tag set (make_tags' `classes`, `unicode` and `mixed`)
   bool variants = false;  // variable-width tags (make_tags' `variants`, with `classes`)
+  bool extended = false;  // shorthands and counted repetition (make_tags' `extended`, with `variants`)
 };
 const ClassSet kClassSets[] = {
     {{"think", "th.nk"},
@@ -95,6 +96,19 @@ const ClassSet kClassSets[] = {
      {"<réflexion>", "</RÉFLEXIONS>", "<R\\u00c9flexions>", "<réflexions?>", "<réflexion", "s>", "<思>", "</思考>", "<思(考)?>",
       "<\\u601d", "考>", "<é>", "</É7>", "<é>>", "<éé>", "<é", "7>"},
      true, true, true},
+    // extended tags: shorthands (a non-ASCII digit, space or letter at their positions, whole and cut
+    // inside the code point) and counted repetition
+    {{"step\\d", "t\\d?", "h[1-6]{1,2}", "sec\\s\\d{1,3}", "n[\\w-]{2}"},
+     {"<step1>", "</STEP1>", "<step\xd9\xa3>", "</step\xd9\xa3>", "<step\\u0663>", "<step\xef\xbc\x93>", "<step", "1>", "\xd9\xa3>",
+      "<step\\\\d>", "<step\\\\", "<stepx>", "<step<>", "<t>", "</t>", "<t5>", "</T5>", "<t\xd9\xa3>", "<t>>", "<h1>", "</H16>", "<h12>",
+      "<h7>", "<h123>", "<h", "<sec 1>", "</SEC\\n12>", "<sec\xc2\xa0" "7>", "<sec\xe3\x80\x80" "123>", "<sec 1234>", "<sec\\t", "<nab>",
+      "</N-_>", "<n\xc3\xa9\xe6\x80\x9d>", "</n\xc3\xa9\xe6\x80\x9d>", "<n\xc3\x89\xe6\x80\x9d>", "<n\xc3\xa9", "<na>", "<n<b>"},
+     false, false, true, true},
+    {{"\xe6\x80\x9d\\d", "r\xc3\xa9" "fl\\w{1,2}"},
+     {"<\xe6\x80\x9d" "7>", "</\xe6\x80\x9d" "7>", "<\xe6\x80\x9d\xd9\xa3>", "</\xe6\x80\x9d\xd9\xa3>", "<\xe6\x80\x9d", "7>", "\xd9\xa3>",
+      "<\xe6\x80\x9d\\\\d>", "<r\xc3\xa9" "flx>", "</R\xc3\x89" "FLXY>", "<r\xc3\xa9" "fl\xc3\xa9>", "</r\xc3\xa9" "fl\xc3\xa9>",
+      "<r\xc3\xa9" "fl\xe6\x80\x9d" "1>", "<r\xc3\xa9" "fl", "x>", "<r\xc3\xa9" "fl >", "<r\xc3\xa9" "fl<>"},
+     true, true, true, true},
 };
 const ClassSet* g_class = nullptr;  // the class tag set of this iteration (null: the default tags)
 
@@ -206,7 +220,8 @@ std::string rand_tag() {
     default: break;
   }
   static const char* kAtoms[] = {"a", "b", "t", "(", ")", "(?:", "|", "?", ".", "[0-9]", "[^a]", "[", "]", "\\.", "\\",
-                                 "*", "+", "{2}", "é", "思", "<", ">", "/", "^", "$", " ", "X"};
+                                 "*", "+", "{2}", "é", "思", "<", ">", "/", "^", "$", " ", "X",
+                                 "{", "}", ",", "0", "1", "2", "6", "9", "\\d", "\\w", "\\s", "\\D", "{1,2}", "{,3}"};
   std::string t;
   const int n = 1 + R(R(4) == 0 ? 70 : 14);
   for (int i = 0; i < n; ++i) t += kAtoms[R(sizeof(kAtoms) / sizeof(kAtoms[0]))];
@@ -219,10 +234,10 @@ bool malformed_tags_hold() {
   std::vector<std::string> tags;
   const int n = 1 + R(3);
   for (int i = 0; i < n; ++i) tags.push_back(rand_tag());
-  const bool unicode = R(2), mixed = R(2), variants = R(4) != 0;
+  const bool unicode = R(2), mixed = R(2), variants = R(4) != 0, extended = R(3) != 0;
   try {
-    const Tags t = make_tags(tags, true, unicode, mixed, variants);
-    const auto rows = tagset_rows(tags, true, unicode, mixed, variants);
+    const Tags t = make_tags(tags, true, unicode, mixed, variants, extended);
+    const auto rows = tagset_rows(tags, true, unicode, mixed, variants, extended);
     if ((int)rows.size() != t.ts.n || t.ts.n > kMaxTags) return false;
     std::string text = "<" + tags[0] + "></" + tags[0] + "><";
     for (const auto& r : rows) text += "<" + r.first + ">x</" + r.first + ">";
@@ -275,7 +290,7 @@ int main(int argc, char** argv) {
     const Tags tags = make_tags(g_class ? g_class->tags : default_tags,
                                 g_class != nullptr && (!g_class->unicode || g_class->mixed),
                                 g_class != nullptr && g_class->unicode, g_class != nullptr && g_class->mixed,
-                                g_class != nullptr && g_class->variants);
+                                g_class != nullptr && g_class->variants, g_class != nullptr && g_class->extended);
     int ns = 1 + R(4);
     std::vector<std::string> bodies;
     std::vector<bool> filt;

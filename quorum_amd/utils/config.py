@@ -307,6 +307,15 @@ class RuntimeConfig:
                "*", "+", "{...}", lazy forms, anchors and shorthands are still refused.  A
                non-ASCII tag of this form needs native_mixed_tags as well.  Off (the default):
                such a tag needs the python engine
+    native_extended_tags: with native_regex_tags and native_variant_tags both on (refused
+               otherwise), the shorthands \\d, \\w and \\s (alone or inside a bracket class) and
+               counted repetition {m}, {m,n}, {,n} (n <= 61) after an element or a group also run on
+               the native engines — "step\\d", "thought_\\d{1,2}", "h[1-6]{1,2}", "phase\\s\\d".  A
+               counted repetition runs as its rows, as '?' does; a non-ASCII character at a
+               shorthand position is decided on the host.  \\D, \\W and \\S (the reference's filter
+               and strip disagree about them), "*", "+", "{m,}", lazy and possessive forms, anchors
+               and the other escapes are still refused.  Off (the default): such a tag needs the
+               python engine
     """
 
     engine: str = "auto"
@@ -334,6 +343,7 @@ class RuntimeConfig:
     native_unicode_tags: bool = False
     native_mixed_tags: bool = False
     native_variant_tags: bool = False
+    native_extended_tags: bool = False
 
     def __post_init__(self):
         if not isinstance(self.native_regex_tags, bool):
@@ -349,6 +359,11 @@ class RuntimeConfig:
             raise ValueError(f"runtime.native_variant_tags must be true or false, got {self.native_variant_tags!r}")
         if self.native_variant_tags and not self.native_regex_tags:
             raise ValueError("runtime.native_variant_tags needs runtime.native_regex_tags true")
+        if not isinstance(self.native_extended_tags, bool):
+            raise ValueError(f"runtime.native_extended_tags must be true or false, got {self.native_extended_tags!r}")
+        if self.native_extended_tags and not (self.native_regex_tags and self.native_variant_tags):
+            raise ValueError("runtime.native_extended_tags needs runtime.native_regex_tags and "
+                             "runtime.native_variant_tags both true")
 
     @classmethod
     def from_config(cls, cfg: Dict[str, Any]) -> "RuntimeConfig":

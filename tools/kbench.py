@@ -9,6 +9,7 @@ QMX_STAGE_TIMING=1) the per-stage wall-time split measured in-kernel with s_memr
 import argparse
 import json
 import os
+import re
 import sys
 import time
 
@@ -79,13 +80,16 @@ def main():
     ap.add_argument("--variants", action="store_true",
                     help="with --classes: variable-width tags ('?', '|', groups: runtime.native_variant_tags), e.g. "
                          "--tags 'think(ing)?,thoughts?' or --tags 't[0-9]?' --body-tag t (the class kernels)")
+    ap.add_argument("--extended", action="store_true",
+                    help="with --classes --variants: shorthands and counted repetition (runtime.native_extended_tags), "
+                         "e.g. --tags 'step\\d,t\\d?' --body-tag step1 or --tags 'h[1-6]{1,2}' --body-tag h12")
     ap.add_argument("--body-tag", default="think",
                     help="mock shape: the think block's tag as the upstream writes it, e.g. réflexion or RÉFLEXION")
     args = ap.parse_args()
     from quorum_amd.ops.native import NativeEngine
 
     body = mock_stream(tag=args.body_tag) if args.shape == "mock" else tagdense_stream()
-    tags = args.tags.split(",")
+    tags = re.split(r",(?![^{]*\})", args.tags)  # (a comma inside a count, "h[1-6]{1,2}", is the tag's)
     results = []
     grid = None
     if args.grid > 0:
@@ -95,7 +99,8 @@ def main():
         # a class tag set runs on a grid of its own kind (the class kernel)
         # (so does a pair tag set: --unicode and a cased non-ASCII character in a tag)
         grid = ext.HipGrid(0, args.grid, 8, classes=(args.classes or args.unicode)
-                           and ext.tagset_has_classes(tags, args.classes, args.unicode, args.mixed, args.variants))
+                           and ext.tagset_has_classes(tags, args.classes, args.unicode, args.mixed, args.variants,
+                                                      args.extended))
     combos = {"ft": (True, True), "f": (True, False), "t": (False, True)}
     for filt, emit in [combos[c] for c in args.combos.split(",")]:
         for n in [int(x) for x in args.slots.split(",")]:
@@ -108,6 +113,8 @@ def main():
                 kw["mixed"] = True
             if args.variants:
                 kw["variants"] = True
+            if args.extended:
+                kw["extended"] = True
             eng = NativeEngine(args.engine, tags, device=0, max_slots=4096, content_cap=1 << 16, **kw)
             walls = []
             evs = [e + b"\n\n" for e in body.split(b"\n\n") if e]
