@@ -25,8 +25,8 @@ namespace {
 struct PyStreamFilter {
   Tags tags;
   FilterState fs;
-  PyStreamFilter(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed, bool variants, bool extended)
-      : tags(make_tags(t, classes, unicode, mixed, variants, extended)) {}
+  PyStreamFilter(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat)
+      : tags(make_tags(t, classes, unicode, mixed, variants, extended, repeat)) {}
   py::bytes feed(const std::string& s) {
     std::string out;
     filter_feed(tags, fs, (const uint8_t*)s.data(), s.size(), out);
@@ -40,8 +40,8 @@ struct PyStreamFilter {
 
 struct PyStripper {
   Tags tags;
-  PyStripper(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed, bool variants, bool extended)
-      : tags(make_tags(t, classes, unicode, mixed, variants, extended)) {}
+  PyStripper(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat)
+      : tags(make_tags(t, classes, unicode, mixed, variants, extended, repeat)) {}
   py::bytes strip(const std::string& s) { return py::bytes(strip_final(tags, (const uint8_t*)s.data(), s.size())); }
 };
 
@@ -144,6 +144,7 @@ ServerCfg server_cfg_from(const py::dict& d) {
   gb("tag_mixed", c.tag_mixed);
   gb("tag_variants", c.tag_variants);
   gb("tag_extended", c.tag_extended);
+  gb("tag_repeat", c.tag_repeat);
   gs("aggregator_name", c.aggregator_name); gs("prompt_template", c.prompt_template);
   gs("intermediate_separator", c.intermediate_separator); gs("query_format", c.query_format);
   gs("source_label_format", c.source_label_format); gb("include_original_query", c.include_original_query);
@@ -481,39 +482,39 @@ PYBIND11_MODULE(_qmx, m) {
     return py::bytes(out);
   });
   py::class_<PyStreamFilter>(m, "StreamFilter")
-      .def(py::init<const std::vector<std::string>&, bool, bool, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
-           py::arg("unicode") = false, py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false)
+      .def(py::init<const std::vector<std::string>&, bool, bool, bool, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
+           py::arg("unicode") = false, py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false)
       .def("feed", &PyStreamFilter::feed)
       .def("flush", &PyStreamFilter::flush);
   py::class_<PyStripper>(m, "Stripper")
-      .def(py::init<const std::vector<std::string>&, bool, bool, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
-           py::arg("unicode") = false, py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false)
+      .def(py::init<const std::vector<std::string>&, bool, bool, bool, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
+           py::arg("unicode") = false, py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false)
       .def("strip", &PyStripper::strip);
   // is this tag list inside what make_tags runs natively (the one definition of the subset)?
-  m.def("tagset_ok", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
+  m.def("tagset_ok", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
     try {
-      make_tags(tags, classes, unicode, mixed, variants, extended);
+      make_tags(tags, classes, unicode, mixed, variants, extended, repeat);
       return true;
     } catch (const std::invalid_argument&) {
       return false;
     }
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
   // why make_tags refuses this tag list ("" when it does not): the limit's own message
-  m.def("tagset_error", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
+  m.def("tagset_error", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
     try {
-      make_tags(tags, classes, unicode, mixed, variants, extended);
+      make_tags(tags, classes, unicode, mixed, variants, extended, repeat);
       return std::string();
     } catch (const std::invalid_argument& e) {
       return std::string(e.what());
     }
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
   // distinct tags of the set make_tags builds ("É" and "é" are one)
-  m.def("tagset_size", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
-    return make_tags(tags, classes, unicode, mixed, variants, extended).ts.n;
+  m.def("tagset_size", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
+    return make_tags(tags, classes, unicode, mixed, variants, extended, repeat).ts.n;
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
   // the case rule of one non-ASCII tag character (qmx_unicode_fold.h): (kind, partner) with
   // kind 0 uncased, 1 a simple case pair, 2 refused; partner: the pair's other member, else cp
   m.def("unicode_tag_char", [](uint32_t cp) {
@@ -522,21 +523,21 @@ PYBIND11_MODULE(_qmx, m) {
     return py::make_tuple(kind, kind == 1 ? unicode_tag_partner(cp) : cp);
   });
   // the kind of the tag set this list makes (qmx_text.h TagKind)
-  m.def("tagset_kind", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
-    const TagKind k = make_tags(tags, classes, unicode, mixed, variants, extended).kind;
+  m.def("tagset_kind", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
+    const TagKind k = make_tags(tags, classes, unicode, mixed, variants, extended, repeat).kind;
     return k == TAGS_MIXED ? "mixed" : k == TAGS_PAIR ? "pair" : k == TAGS_CLASS ? "class" : "literal";
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
   // of the class kind (class, pair or mixed)?  Such a tag set's engines need HipGrid(classes=True)
-  m.def("tagset_has_classes", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
-    return make_tags(tags, classes, unicode, mixed, variants, extended).kind != TAGS_LITERAL;
+  m.def("tagset_has_classes", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
+    return make_tags(tags, classes, unicode, mixed, variants, extended, repeat).kind != TAGS_LITERAL;
   }, py::arg("tags"), py::arg("classes") = true, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
   // candidates '<' of `text` the GPU kernels would hand to the host path (qmx_text.h
   // class_candidate, the shared suspect rule), with the streaming or the strip tables
   m.def("class_suspects", [](const std::vector<std::string>& tags, const std::string& text, bool strip, bool unicode,
-                             bool mixed, bool variants, bool extended) {
-    const Tags t = make_tags(tags, true, unicode, mixed, variants, extended);
+                             bool mixed, bool variants, bool extended, bool repeat) {
+    const Tags t = make_tags(tags, true, unicode, mixed, variants, extended, repeat);
     int k = 0;
     if (t.kind == TAGS_LITERAL) return k;
     const uint8_t* x = (const uint8_t*)text.data();
@@ -549,24 +550,24 @@ PYBIND11_MODULE(_qmx, m) {
     }
     return k;
   }, py::arg("tags"), py::arg("text"), py::arg("strip") = false, py::arg("unicode") = false, py::arg("mixed") = false,
-     py::arg("variants") = false, py::arg("extended") = false);
+     py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
   // the rows of the set make_tags builds: (row text, index of its tag in `tags`), in order — a
   // variable-width tag (`variants`) has one row per fixed-width expansion, every other tag one
-  m.def("tagset_rows", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
+  m.def("tagset_rows", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
     py::list out;
-    for (const auto& r : tagset_rows(tags, classes, unicode, mixed, variants, extended))
+    for (const auto& r : tagset_rows(tags, classes, unicode, mixed, variants, extended, repeat))
       out.append(py::make_tuple(py::bytes(r.first).attr("decode")("utf-8"), r.second));
     return out;
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false, py::arg("mixed") = false,
-     py::arg("variants") = false, py::arg("extended") = false);
+     py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
   env_refresh();
   py::class_<CpuEngine> ce(m, "CpuEngine");
-  ce.def(py::init([](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended) {
+  ce.def(py::init([](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
            env_refresh();
-           return new CpuEngine(make_tags(tags, classes, unicode, mixed, variants, extended));
+           return new CpuEngine(make_tags(tags, classes, unicode, mixed, variants, extended, repeat));
          }),
          py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
   bind_engine(ce);
   // the multi-door grid of loop ticks (tests drive several door engines from Python threads)
   py::class_<HipGrid>(m, "HipGrid")
@@ -612,15 +613,15 @@ PYBIND11_MODULE(_qmx, m) {
   py::class_<HipEngine> he(m, "HipEngine");
   he.def(py::init([](const std::vector<std::string>& tags, int device, int tile, int max_slots, int content_cap,
                       int lanes, HipGrid* grid, int door, int ndoors, bool classes, bool unicode, bool mixed,
-                      bool variants, bool extended) {
+                      bool variants, bool extended, bool repeat) {
            env_refresh();
-           return new HipEngine(make_tags(tags, classes, unicode, mixed, variants, extended), device, tile, max_slots, content_cap, lanes, grid,
+           return new HipEngine(make_tags(tags, classes, unicode, mixed, variants, extended, repeat), device, tile, max_slots, content_cap, lanes, grid,
                                 door, ndoors);
          }),
          py::arg("tags"), py::arg("device"), py::arg("tile_bytes") = 16384, py::arg("max_slots") = 8192,
          py::arg("content_cap") = 1 << 20, py::arg("lanes") = 1, py::arg("grid") = nullptr, py::arg("door") = -1,
          py::arg("ndoors") = 1, py::arg("classes") = false, py::arg("unicode") = false, py::arg("mixed") = false,
-         py::arg("variants") = false, py::arg("extended") = false, py::keep_alive<1, 8>());
+         py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::keep_alive<1, 8>());
   bind_engine(he);
   he.def("kernel_stats", &HipEngine::kernel_stats);
   he.def("debug_poison_results", &HipEngine::debug_poison_results, py::arg("ahead") = 1);

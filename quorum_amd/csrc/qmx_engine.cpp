@@ -25,6 +25,7 @@ struct Elem {
   uint8_t lit = 0;
   uint32_t tab[4] = {0, 0, 0, 0};
   uint8_t flags = 0;
+  bool rep = false;  // the open-ended copy of an unbounded repetition: this element, once or more
   std::string txt;  // as written (a plain literal lowered): tagset_rows
 };
 
@@ -38,6 +39,10 @@ const char* kUpperShorthand =
     "tag holds \\D, \\W or \\S: the reference's streaming filter compiles the lowercased tag (\\d, \\w, \\s) and its "
     "final strip the tag as written, so the two disagree (runs with --impl python): ";
 const char* kEmptyRepeat = "tag repeats a group that can match the empty string (runs with --impl python): ";
+const char* kUnboundedGroup = "tag repeats a group without a bound (runs with --impl python): ";
+const char* kRepeatOverlap =
+    "tag repeats an element that also accepts what can follow the run, so the run's end depends on the regex's "
+    "backtracking (runs with --impl python): ";
 
 // The shorthand at t[i] == '\\' (make_tags' `extended`): its ASCII table is or-ed into tab and its
 // flag bit returned; 0: no shorthand there.  \D, \W and \S are refused with their own message.
@@ -176,7 +181,7 @@ typedef std::vector<Elem> Row;
 typedef std::vector<Row> Rows;  // in priority order, no two equal
 
 bool same_elem(const Elem& a, const Elem& b) {
-  if (a.cls != b.cls) return false;
+  if (a.cls != b.cls || a.rep != b.rep) return false;
   return a.cls ? a.flags == b.flags && std::memcmp(a.tab, b.tab, sizeof(a.tab)) == 0 : a.lit == b.lit;
 }
 bool same_row(const Row& a, const Row& b) {
@@ -211,6 +216,7 @@ struct VariantParser {
   const std::string& t;
   bool wide;
   bool extended;  // shorthands, and counted repetition after an atom
+  bool repeat;    // with extended: '+', '*' and "{m,}" after one element (VariantParser::unbounded)
   size_t i = 0;
   bool ops = false;  // a '?', a '|' or a group was read: a variable-width tag
 
@@ -228,7 +234,8 @@ struct VariantParser {
     out.assign(1, Row());
     while (i < t.size() && t[i] != '|' && t[i] != ')') {
       Rows a;
-      if (t[i] == '(') {
+      const bool group = t[i] == '(';
+      if (group) {
         if (depth >= kMaxTagLen) return false;
         ops = true;
         ++i;
@@ -244,7 +251,11 @@ struct VariantParser {
         a.assign(1, Row(1, e));
       }
       if (extended && i < t.size() && t[i] == '{') {
-        if (!counted(a)) return false;
+        if (!counted(a, group)) return false;
+      } else if (repeat && i < t.size() && (t[i] == '+' || t[i] == '*')) {
+        const int m = t[i] == '+' ? 1 : 0;
+        ++i;
+        if (!unbounded(a, group, m, m == 0 ? kRepeatRows : m + kRepeatRows - 1)) return false;
       } else if (i < t.size() && t[i] == '?') {  // greedy: present, then absent; "??", "?+", "?*", "?{" are refused
         ops = true;
         ++i;
@@ -268,7 +279,34 @@ struct VariantParser {
       for (const Row& y : r) add_row(out, join_rows(x, y));
     return out;
   }
-  bool counted(Rows& a) {
+  // '+', '*' or "{m,}" was read after the atom whose rows are `a`; i is after it.  It expands as
+  // x{m, top} does, longest first, and the longest row is open-ended at its last copy of x: "top or
+  // more".  Only one element repeats: a group is refused with its own message, a non-ASCII literal
+  // (one element per byte), a lazy form and a stacked quantifier with the regex one.  The open-ended
+  // copy of a literal is kept as a class of that one letter, so the class walks see the row.
+  // (What may follow the run is checked over the whole tag's rows: repeat_overlap.)
+  bool unbounded(Rows& a, bool group, int m, int top) {
+    if (i < t.size() && std::strchr("?+*{", t[i])) return false;
+    if (group) throw TagRefusal{kUnboundedGroup};
+    const Elem x = a[0][0];
+    if (!x.cls && x.lit >= 0x80) return false;
+    ops = true;
+    Elem open = x;
+    if (!open.cls) {
+      open.cls = true;
+      tab_set(open.tab, x.lit);
+    }
+    open.rep = true;
+    a.clear();
+    for (int n = top; n >= m; --n) {
+      if (n > kMaxTagLen) throw RowTooLong();
+      Row r((size_t)n, x);
+      if (n == top) r.back() = open;
+      add_row(a, r);
+    }
+    return true;
+  }
+  bool counted(Rows& a, bool group) {
     size_t j = i + 1;
     auto number = [&](int* v) {  // up to three digits ("061" is 61, the largest count); a longer run is refused
       const size_t j0 = j;
@@ -280,6 +318,11 @@ struct VariantParser {
     const bool has_m = number(&m);
     if (j < t.size() && t[j] == ',') {
       ++j;
+      if (repeat && has_m && j < t.size() && t[j] == '}') {  // "{m,}"
+        if (m > kMaxTagLen) return false;
+        i = j + 1;
+        return unbounded(a, group, m, m + kRepeatRows - 1);
+      }
       if (!number(&n)) return false;  // "{m,}" is unbounded, "{,}" a literal
     } else {
       if (!has_m) return false;
@@ -305,27 +348,58 @@ struct VariantParser {
 };
 
 // The rows of one tag; *ops: it is a variable-width tag.  False outside the subset.
-bool parse_variant_tag(const std::string& t, Rows& out, bool wide, bool extended, bool* ops) {
-  VariantParser p{t, wide, extended};
+// The overlap rule of unbounded repetition.  X: the class of an open-ended element; F: what stands
+// directly after it in a row — the next element, or '>' where the run ends the tag (every follower of
+// the quantifier stands after the open-ended copy in some row: the expansion distributes).  Where X
+// and F share no character the run takes exactly the maximal run of X characters, the text has at
+// most one parse and the quantifier has the matches of the alternation over its counts, in any
+// order: what the rows are.  Where they share one the regex backtracks into the run: refused.  The
+// ASCII tables are compared as built (under IGNORECASE); two elements that can both take a code
+// point >= 0x80 are taken to overlap (the rule errs by refusing only).
+bool repeat_overlap(const Rows& rows) {
+  for (const Row& r : rows)
+    for (size_t i = 0; i < r.size(); ++i) {
+      if (!r[i].rep) continue;
+      const Elem& x = r[i];
+      if (i + 1 == r.size()) {
+        if ((x.tab['>' >> 5] >> ('>' & 31)) & 1u) return true;
+        continue;
+      }
+      const Elem& f = r[i + 1];
+      const bool xw = (x.flags & (CLS_WIDE | CLS_SH)) != 0;
+      if (!f.cls) {
+        if (f.lit >= 0x80 ? xw : ((x.tab[f.lit >> 5] >> (f.lit & 31)) & 1u) != 0) return true;
+        continue;
+      }
+      if (xw && (f.flags & (CLS_WIDE | CLS_SH))) return true;
+      for (int k = 0; k < 4; ++k)
+        if (x.tab[k] & f.tab[k]) return true;
+    }
+  return false;
+}
+
+bool parse_variant_tag(const std::string& t, Rows& out, bool wide, bool extended, bool repeat, bool* ops) {
+  VariantParser p{t, wide, extended, repeat};
   if (!p.alt(out, 0) || p.i != t.size()) return false;
+  if (repeat && repeat_overlap(out)) throw TagRefusal{kRepeatOverlap};
   *ops = p.ops;
   return true;
 }
 
 Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants,
-                bool extended, std::vector<std::pair<std::string, int>>* rows_out);
+                bool extended, bool repeat, std::vector<std::pair<std::string, int>>* rows_out);
 
 }  // namespace
 
 Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants,
-               bool extended) {
-  return build_tags(tags, classes, unicode, mixed, variants, extended, nullptr);
+               bool extended, bool repeat) {
+  return build_tags(tags, classes, unicode, mixed, variants, extended, repeat, nullptr);
 }
 
 std::vector<std::pair<std::string, int>> tagset_rows(const std::vector<std::string>& tags, bool classes, bool unicode,
-                                                     bool mixed, bool variants, bool extended) {
+                                                     bool mixed, bool variants, bool extended, bool repeat) {
   std::vector<std::pair<std::string, int>> rows;
-  build_tags(tags, classes, unicode, mixed, variants, extended, &rows);
+  build_tags(tags, classes, unicode, mixed, variants, extended, repeat, &rows);
   return rows;
 }
 
@@ -357,10 +431,11 @@ uint32_t unicode_tag_partner(uint32_t cp) {
 
 namespace {
 Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants,
-                bool extended, std::vector<std::pair<std::string, int>>* rows_out) {
+                bool extended, bool repeat, std::vector<std::pair<std::string, int>>* rows_out) {
   mixed = mixed && classes && unicode;
   variants = variants && classes;
   extended = extended && variants;
+  repeat = repeat && extended;
   Tags out;
   std::memset(&out, 0, sizeof(out));
   TagSet& ts = out.ts;
@@ -447,7 +522,7 @@ Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode
         const bool w = wide && unicode;
         rows.clear();
         try {
-          ok = parse_variant_tag(w ? tw : t0, rows, w, extended, &var);
+          ok = parse_variant_tag(w ? tw : t0, rows, w, extended, repeat, &var);
         } catch (const TooManyRows&) {
           throw std::invalid_argument("thinking tags expand to more than 16 rows: " + t0);
         } catch (const RowTooLong&) {
@@ -497,7 +572,7 @@ Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode
       if (var) tc.var |= 1u << ts.n;
       if (rows_out) {
         std::string txt = literal ? t : std::string();
-        for (const Elem& e : elems) txt += e.txt;
+        for (const Elem& e : elems) txt += e.rep ? e.txt + "+" : e.txt;  // (open-ended: this element, once or more)
         rows_out->emplace_back(txt, (int)ti);
       }
       if (has_pair) pair_tags |= 1u << ts.n;
@@ -516,6 +591,7 @@ Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode
             continue;
           }
           tc.clsmask[ts.n] |= 1ull << i;
+          if (e.rep) tc.rep[ts.n] |= 1ull << i;
           int k = 0;
           while (k < tc.n && !(tc.flags[k] == e.flags && std::memcmp(tc.tab[k], e.tab, sizeof(e.tab)) == 0)) ++k;
           if (k == tc.n) {

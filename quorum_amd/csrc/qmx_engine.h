@@ -50,13 +50,18 @@ struct Tags {
 // members of a bracket class; a class with one holds some code points >= 0x80, which the host
 // walks look up in qmx_unicode_classes.h and the kernels leave to the host) and counted
 // repetition {m}, {m,n}, {,n} after an element or a group, which expands into rows as '?' does
+// repeat: with extended, also accept '+', '*' and "{m,}" after one element whose class shares no
+// character with what can follow the run.  It expands into kRepeatRows rows beyond its minimum
+// count, the longest of them open-ended at its last copy (TagClasses::rep): the host walks take the
+// rest of the run there, the kernels leave a longer run to the host
 Tags make_tags(const std::vector<std::string>& tags, bool classes = false, bool unicode = false, bool mixed = false,
-               bool variants = false, bool extended = false);
-// The rows of the set make_tags builds, in order, as text (a class position as "." or "[]"),
-// each with the index of its tag in `tags` (tests, tools/kbench.py)
+               bool variants = false, bool extended = false, bool repeat = false);
+// The rows of the set make_tags builds, in order, as text (a class position as "." or "[]"; an
+// open-ended position — this element, once or more — as the element and a '+'), each with the index
+// of its tag in `tags` (tests, tools/kbench.py)
 std::vector<std::pair<std::string, int>> tagset_rows(const std::vector<std::string>& tags, bool classes = false,
                                                      bool unicode = false, bool mixed = false, bool variants = false,
-                                                     bool extended = false);
+                                                     bool extended = false, bool repeat = false);
 // the case rule of a non-ASCII tag character: 0 uncased, 1 a pair (*lower: its lower member), 2 refused
 int unicode_tag_char(uint32_t cp, uint32_t* lower);
 uint32_t unicode_tag_partner(uint32_t cp);  // the other member of cp's pair (cp: none)

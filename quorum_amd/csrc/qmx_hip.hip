@@ -507,7 +507,7 @@ __device__ __noinline__ int mixed_hold_dev(const uint8_t* x, int q, int e, const
     return (pre ? 1 : 0) | (tk > 0 && !pre ? 2 : 0);
   }
   const int r = mixed_prefix(x, q, e, *ts, *tc);
-  return r == kWalkHost ? 2 : r;  // (a byte >= 0x80 at a class with a shorthand: the host decides the tile)
+  return r == kWalkHost ? 2 : r;  // (a byte >= 0x80 at a class with a shorthand, a run past an open-ended row: the host decides the tile)
 }
 // the first in list order of the fast matchers' token and the walk's
 __device__ __forceinline__ int mixed_first(int lit, int tok) {
@@ -530,8 +530,8 @@ __device__ __forceinline__ int class_token(const uint8_t* Z, int Zn, int p, cons
 // block the reference holds what is a prefix of a tag's SOURCE text, so an open tag whose
 // first part was released at this cut is no token at all: bit 1, the tile goes to the host.
 // Inside a block: a proper class-aware prefix of any pattern — or, where the walk meets a byte
-// >= 0x80 at a class with a shorthand (kWalkHost), bit 1 again: never "no prefix", which would
-// release held text.  Bit 0: hold.
+// >= 0x80 at a class with a shorthand, or one more copy after an open-ended row's last one
+// (kWalkHost), bit 1 again: never "no prefix", which would release held text.  Bit 0: hold.
 __device__ __forceinline__ int class_hold(const uint8_t* Z, int q, int e, const KParams& P, int dq, int tk) {
   if (e - q > kMaxTail) return 0;
   if (is_pair_set(*P.cls)) return fold_prefix_dev(Z, q, e, &P.ts, P.cls, dq == 0);
@@ -541,7 +541,7 @@ __device__ __forceinline__ int class_hold(const uint8_t* Z, int q, int e, const 
     return (pre ? 1 : 0) | (tk > 0 && !pre ? 2 : 0);
   }
   const int r = class_prefix(Z, q, e, P.ts, *P.cls);
-  return r == kWalkHost ? 2 : r;  // (a byte >= 0x80 at a class with a shorthand: the host decides the tile)
+  return r == kWalkHost ? 2 : r;  // (a byte >= 0x80 at a class with a shorthand, a run past an open-ended row: the host decides the tile)
 }
 
 // holdback test at stream position e (Z coords): returns cut (q when held, else e).

@@ -63,6 +63,7 @@ struct ServerCfg {
   bool tag_mixed = false;    // runtime.native_mixed_tags: with both, class and non-ASCII tags in one set and one tag
   bool tag_variants = false;  // runtime.native_variant_tags: with tag_classes, tags with '?', '|' and groups run natively
   bool tag_extended = false;  // runtime.native_extended_tags: with tag_variants, the shorthands d, w, s and counted repetition run natively
+  bool tag_repeat = false;    // runtime.native_repeat_tags: with tag_extended, '+', '*' and "{m,}" after one element run natively
   // strategy.aggregate (consulted whatever strategy is selected, as in quorum)
   std::string aggregator_name;  // empty = none
   std::string prompt_template, intermediate_separator, query_format, source_label_format;

@@ -91,8 +91,18 @@ struct TagClasses {
   // the extended language; the finalize of such a class set goes on to a tag's next close where
   // the first is not the open's captured text (`step\d`: <step1>a</step2>b</step1>).
   uint32_t var;
+  // Unbounded repetition (make_tags(..., repeat = true): '+', '*', "{m,}" after one element).  Such
+  // a quantifier expands as x{m, m + kRepeatRows - 1} does, and the longest row is open-ended at
+  // its last copy of x: "this many or more".  rep[t]: bit i — position i of name[t] (always a class
+  // position: the same convention as clsmask) is open-ended; 0 for every other row and set.  The last
+  // field, read only at a class position that has matched.
+  uint64_t rep[kMaxTags];
 };
 constexpr uint32_t kVarRows = 0xffffu, kVarExtended = 1u << 31;
+// Rows an unbounded quantifier expands into beyond its minimum count: `x+` is the counts 4, 3, 2, 1
+// (`x*`: and 0), `x{m,}` m+3 ... m.  Runs up to the longest row's count are decided by the rows (on
+// the GPU); a longer run is decided by the exact host walk.
+constexpr int kRepeatRows = 4;
 // The kernels of the class kind run class, pair and mixed tag sets (KParams::cls is set for all
 // three): which of them the tables are.
 QMX_HD bool is_pair_set(const TagClasses& tc) { return tc.nfold > 0; }
@@ -109,6 +119,7 @@ struct TagSet {
 };
 
 QMX_HD uint8_t lower_ascii(uint8_t c) { return (c >= 'A' && c <= 'Z') ? (uint8_t)(c + 32) : c; }
+QMX_HD int utf8_lead_len(uint8_t c) { return c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : c >= 0xC0 ? 2 : 1; }
 
 // Pattern byte i of pattern `pat` (pat < n: open "<t>", pat >= n: close "</t>").
 QMX_HD int pattern_len(const TagSet& ts, int pat) {
@@ -202,10 +213,65 @@ QMX_HD int shorthand_char_at(const R& x, int n, int s, uint8_t f, int ln) {  // 
 #endif
 }
 
+// Open-ended positions (TagClasses::rep).  Does the repeated class k accept the byte c as one more
+// copy, as far as a byte tells: its ASCII table, or a byte >= 0x80 where the class holds any (wide,
+// or a shorthand — which code points, only the host knows)?
+QMX_HD bool repeat_accepts(const TagClasses& tc, int k, uint8_t c, bool strip) {
+  return c < 0x80 ? class_accepts(tc, k, c, strip) : (tc.flags[k] & (CLS_WIDE | CLS_SH)) != 0;
+}
+// The host walks take a run past the row's copies; the device walks never do (kWalkHost), so the
+// byte lengths they see are the rows', bounded by make_tags.
+#ifdef __HIP_DEVICE_COMPILE__
+constexpr bool kWalkRuns = false;
+#else
+constexpr bool kWalkRuns = true;
+#endif
+// The run after the copies of an open-ended position of class k, *s the index after the last copy
+// and s0 where the tag's name starts.  Host: consumes while the class accepts the next character
+// (the element's own logic: ASCII table, wide, shorthand ranges).  1: the run ended before a
+// character it does not accept (*s after the run);  -1: the text ended inside the run, or inside
+// a character of it;  0: the name would pass kMaxTagLen bytes — "</" + match + ">" is at most
+// kMaxTail, the holdback's size — which is no match.  Device: 1 where the next byte is not
+// accepted (or the text ended: the caller's proper prefix), kWalkHost where it is.
+// (Out of line, as the mixed walks are: the class kernels keep their register budget —
+// tests/test_isa_class_grid.py — and only a set with an open-ended row comes here.)
+template <class R>
+__attribute__((noinline)) QMX_HD int repeat_run(const R& x, int n, int* s, int s0, const TagClasses& tc, int k, bool strip) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return *s < n && repeat_accepts(tc, k, x[*s], strip) ? kWalkHost : 1;
+#else
+  const uint8_t f = tc.flags[k];
+  int q = *s;
+  while (true) {
+    if (q >= n) return -1;
+    const uint8_t c = x[q];
+    int ln = 1;
+    if (c < 0x80) {
+      if (!class_accepts(tc, k, c, strip)) break;
+    } else {
+      if (!(f & (CLS_WIDE | CLS_SH))) break;
+      ln = utf8_lead_len(c);
+      if (q + ln - s0 > kMaxTagLen) return 0;  // (no follower of such a class takes a byte >= 0x80: no match either way)
+      if (f & CLS_SH) {
+        const int r = shorthand_char_at(x, n, q, f, ln);
+        if (r == 0) break;
+        if (r != 1) return r;
+      }
+      if (q + ln > n) return -1;
+    }
+    if (q + ln - s0 > kMaxTagLen) return 0;
+    q += ln;
+  }
+  *s = q;
+  return 1;
+#endif
+}
+
 // Walk pattern `pat` (pat < n: "<t>", else "</t>") over x[p:n).  1: it matches, *end is the
 // index after its '>';  0: mismatch;  -1: every byte of x[p:n) matched and the text ended
 // before the pattern did (a proper prefix — a code point cut short at n counts as one);
-// kWalkHost: device code met a byte >= 0x80 at a class with a shorthand (shorthand_char_at).
+// kWalkHost: device code met a byte >= 0x80 at a class with a shorthand (shorthand_char_at), or one
+// more copy after an open-ended position (repeat_run).
 template <class R>
 QMX_HD int class_walk(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, int pat, bool strip,
                       int* end) {
@@ -220,25 +286,36 @@ QMX_HD int class_walk(const R& x, int n, int p, const TagSet& ts, const TagClass
     if (x[s] != '/') return 0;
     ++s;
   }
+  const int s0 = s;     // the name starts here; opened: a run was taken, so its length is no longer the row's
+  bool opened = false;
   for (int i = 0; i < ts.len[t]; ++i) {
+    if (kWalkRuns && opened && s - s0 >= kMaxTagLen) return 0;
     if (s >= n) return -1;
     const uint8_t c = x[s], e = ts.name[t][i];
     if (e < 0x80) {
       if (lower_ascii(c) != e) return 0;
       ++s;
-    } else if (c < 0x80) {
+      continue;
+    }
+    if (c < 0x80) {
       if (!class_accepts(tc, e - 0x80, c, strip)) return 0;
       ++s;
     } else {
       const uint8_t f = tc.flags[e - 0x80];
       if (!(f & (CLS_WIDE | CLS_SH))) return 0;
       const int ln = c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : c >= 0xC0 ? 2 : 1;
+      if (kWalkRuns && opened && s + ln - s0 > kMaxTagLen) return 0;
       if (f & CLS_SH) {
         const int r = shorthand_char_at(x, n, s, f, ln);
         if (r != 1) return r;
       }
       if (s + ln > n) return -1;
       s += ln;
+    }
+    if (__builtin_expect((tc.rep[t] >> i) & 1, 0)) {
+      const int r = repeat_run(x, n, &s, s0, tc, e - 0x80, strip);
+      if (r != 1) return r;
+      opened = true;
     }
   }
   if (s >= n) return -1;
@@ -285,6 +362,17 @@ QMX_HD bool variant_mismatch(const TagClasses& tc, int k, uint8_t c) {
   if ((tc.var & kVarRows) == 0) return false;
   return c >= 0x80 ? !(tc.flags[k] & (CLS_WIDE | CLS_SH)) : !((tc.tab[k][c >> 5] >> (c & 31)) & 1u);
 }
+// An open-ended position (TagClasses::rep) of row t has matched its last copy and the byte after it,
+// x[q], where the follower or the '>' should stand, is one the repeated class accepts: the run is
+// longer than the row, so the token's length is not the row's — suspect, the host's exact walk decides.
+// (Out of line as repeat_run is, the test of the bit too: in line, even that one load takes the
+// class grid kernel past its 256 VGPRs — profiles/repeat_tags/NOTES.md.)
+template <class R>
+__attribute__((noinline)) QMX_HD bool repeat_suspect(const R& x, int n, int q, const TagClasses& tc, int t, int i, int k,
+                                                     bool strip) {
+  if (((tc.rep[t] >> i) & 1) == 0) return false;
+  return q < n && repeat_accepts(tc, k, x[q], strip);
+}
 template <class R>
 QMX_HD int class_candidate(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, bool strip, int* tok,
                            int* tok_len) {
@@ -307,7 +395,10 @@ QMX_HD int class_candidate(const R& x, int n, int p, const TagSet& ts, const Tag
       else if (c == '<' || c == '>' || c >= 0x80) {
         if (!variant_mismatch(tc, e - 0x80, c)) return CC_SUSPECT;
         ok = false;
-      } else ok = class_accepts(tc, e - 0x80, c, strip);
+      } else {
+        ok = class_accepts(tc, e - 0x80, c, strip);
+        if (ok && repeat_suspect(x, n, s0 + i + 1, tc, t, i, e - 0x80, strip)) return CC_SUSPECT;
+      }
     }
     if (ok && res == CC_NONE && s0 + L < n && x[s0 + L] == '>') {
       res = CC_MATCH;
@@ -436,8 +527,6 @@ QMX_HD int fold_char_at(const R& x, int n, int s, uint32_t want, int ln, const T
   }
   return av < ln ? -1 : 1;
 }
-QMX_HD int utf8_lead_len(uint8_t c) { return c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : c >= 0xC0 ? 2 : 1; }
-
 // class_walk for a mixed tag set: a class position is one the tag's bitmap names, every other
 // byte >= 0x80 of name[] starts or continues a literal character, compared with the text folded.
 template <class R>
@@ -455,7 +544,10 @@ QMX_HD int mixed_walk(const R& x, int n, int p, const TagSet& ts, const TagClass
     if (x[s] != '/') return 0;
     ++s;
   }
+  const int s0 = s;  // (as in class_walk)
+  bool opened = false;
   for (int i = 0; i < ts.len[t];) {
+    if (kWalkRuns && opened && s - s0 >= kMaxTagLen) return 0;
     if (s >= n) return -1;
     const uint8_t c = x[s], e = ts.name[t][i];
     if ((cm >> i) & 1) {
@@ -467,12 +559,18 @@ QMX_HD int mixed_walk(const R& x, int n, int p, const TagSet& ts, const TagClass
         const uint8_t f = tc.flags[k];
         if (!(f & (CLS_WIDE | CLS_SH))) return 0;
         const int ln = utf8_lead_len(c);
+        if (kWalkRuns && opened && s + ln - s0 > kMaxTagLen) return 0;
         if (f & CLS_SH) {
           const int r = shorthand_char_at(x, n, s, f, ln);
           if (r != 1) return r;
         }
         if (s + ln > n) return -1;
         s += ln;
+      }
+      if (__builtin_expect((tc.rep[t] >> i) & 1, 0)) {
+        const int r = repeat_run(x, n, &s, s0, tc, k, strip);
+        if (r != 1) return r;
+        opened = true;
       }
       ++i;
     } else if (e < 0x80) {
@@ -481,6 +579,7 @@ QMX_HD int mixed_walk(const R& x, int n, int p, const TagSet& ts, const TagClass
       ++i;
     } else {
       const int ln = utf8_lead_len(e);
+      if (kWalkRuns && opened && s + ln - s0 > kMaxTagLen) return 0;
       uint32_t want = 0;
       for (int k = 0; k < ln; ++k) want |= (uint32_t)ts.name[t][i + k] << (8 * k);
       const int r = fold_char_at(x, n, s, want, ln, tc);
@@ -539,6 +638,7 @@ QMX_HD int mixed_candidate(const R& x, int n, int p, const TagSet& ts, const Tag
           ok = false;
         } else {
           ok = class_accepts(tc, e - 0x80, c, strip);
+          if (ok && repeat_suspect(x, n, s0 + i + 1, tc, t, i, e - 0x80, strip)) return CC_SUSPECT;
         }
         ++i;
       } else if (e < 0x80) {

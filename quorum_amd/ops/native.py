@@ -52,21 +52,21 @@ def gpu_available() -> bool:
 
 
 def sent_tags(tags: Sequence[str], classes: bool = False, unicode: bool = False, mixed: bool = False,
-              variants: bool = False, extended: bool = False) -> List[str]:
+              variants: bool = False, extended: bool = False, repeat: bool = False) -> List[str]:
     """The tag list as it is sent to the extension, first occurrence only.  Class and non-ASCII
     tags go down as written (lowercasing would turn "[Z-a]" into another pattern; the C++ parser
     folds non-ASCII tags through its pair table), plain tags through ``str.lower()``, which is
     more than ASCII lowercasing: "THIN\u212a" (Kelvin sign) is "think" and runs; as written it would not.
-    (``mixed`` needs both other keys, ``variants`` needs ``classes`` and ``extended`` needs ``variants``,
-    so they change nothing here.)"""
+    (``mixed`` needs both other keys, ``variants`` needs ``classes``, ``extended`` needs ``variants``
+    and ``repeat`` needs ``extended``, so they change nothing here.)"""
     return list(dict.fromkeys(t if classes or unicode or mixed else t.lower() for t in tags))
 
 
 def strip_fn(tags: Sequence[str], classes: bool = False, unicode: bool = False,
-             mixed: bool = False, variants: bool = False, extended: bool = False) -> Callable[[str, bool], str]:
+             mixed: bool = False, variants: bool = False, extended: bool = False, repeat: bool = False) -> Callable[[str, bool], str]:
     ext = require()
     stripper = ext.Stripper(sent_tags(tags, classes, unicode, mixed), classes=bool(classes), unicode=bool(unicode),
-                            mixed=bool(mixed), variants=bool(variants), extended=bool(extended))
+                            mixed=bool(mixed), variants=bool(variants), extended=bool(extended), repeat=bool(repeat))
 
     def _strip(text, on):
         if not on:
@@ -79,47 +79,52 @@ def strip_fn(tags: Sequence[str], classes: bool = False, unicode: bool = False,
 
 
 def tagset_rows(tags: Sequence[str], classes: bool = False, unicode: bool = False, mixed: bool = False,
-                variants: bool = False, extended: bool = False) -> List[tuple]:
+                variants: bool = False, extended: bool = False, repeat: bool = False) -> List[tuple]:
     """The rows of the tag set the extension builds from ``tags``: ``(row text, index of its tag)``
     in matching order.  A variable-width tag (``variants``) has one row per fixed-width expansion
-    in the regex's priority order ("think(ing)?": "thinking", "think"); every other tag has one."""
+    in the regex's priority order ("think(ing)?": "thinking", "think"); every other tag has one.
+    With ``repeat`` an unbounded quantifier has ``kRepeatRows`` (4) rows beyond its minimum count,
+    and the longest is open-ended: its last copy is written with a ``+`` after it and stands for
+    "this element, once or more" ("step\\d+": "step\\d\\d\\d\\d+", "step\\d\\d\\d", "step\\d\\d", "step\\d")."""
     return [(str(r), int(i)) for r, i in require().tagset_rows([str(t) for t in tags], bool(classes), bool(unicode),
-                                                               bool(mixed), bool(variants), bool(extended))]
+                                                               bool(mixed), bool(variants), bool(extended), bool(repeat))]
 
 
 def tagset_ok(tags: Sequence[str], classes: bool = False, unicode: bool = False, mixed: bool = False,
-              variants: bool = False, extended: bool = False) -> bool:
+              variants: bool = False, extended: bool = False, repeat: bool = False) -> bool:
     """Does the extension run this tag list natively (``make_tags`` is the one definition)?"""
     return bool(require().tagset_ok([str(t) for t in tags], bool(classes), bool(unicode), bool(mixed),
-                                    bool(variants), bool(extended)))
+                                    bool(variants), bool(extended), bool(repeat)))
 
 
 def tagset_kind(tags: Sequence[str], classes: bool = False, unicode: bool = False, mixed: bool = False,
-                variants: bool = False, extended: bool = False) -> str:
+                variants: bool = False, extended: bool = False, repeat: bool = False) -> str:
     """"literal", "class", "pair" or "mixed": the kind of the tag set this list makes."""
     return str(require().tagset_kind([str(t) for t in tags], bool(classes), bool(unicode), bool(mixed),
-                                     bool(variants), bool(extended)))
+                                     bool(variants), bool(extended), bool(repeat)))
 
 
 def class_suspects(tags: Sequence[str], text: bytes, strip: bool = False, unicode: bool = False,
-                   mixed: bool = False, variants: bool = False, extended: bool = False) -> int:
+                   mixed: bool = False, variants: bool = False, extended: bool = False, repeat: bool = False) -> int:
     """Candidates '<' of ``text`` the GPU kernels would hand to the host path."""
     return int(require().class_suspects([str(t) for t in tags], bytes(text), bool(strip), bool(unicode),
-                                        bool(mixed), bool(variants), bool(extended)))
+                                        bool(mixed), bool(variants), bool(extended), bool(repeat)))
 
 
 def make_grid(tags: Sequence[str], device: int, doors: int, wg_per_door: int = 8, idle_ms: int = 50,
-              classes: bool = False, unicode: bool = False, mixed: bool = False, variants: bool = False, extended: bool = False):
+              classes: bool = False, unicode: bool = False, mixed: bool = False, variants: bool = False, extended: bool = False,
+              repeat: bool = False):
     """A multi-door loop-tick grid (``HipGrid``) of the kind this tag set's engines need: the
     class kernel for a class tag set (``classes`` on and a '.' or bracket class in a tag), for
     a pair tag set (``unicode`` on and a cased non-ASCII character in a tag) and for a mixed tag
     set (``mixed`` on with both, class elements and non-ASCII literals in one set) and for a set
     with a variable-width tag (``variants`` on with ``classes``: '?', '|', groups; ``extended`` on
-    with ``variants``: shorthands and counted repetition), the literal
+    with ``variants``: shorthands and counted repetition; ``repeat`` on with ``extended``: '+', '*'
+    and "{m,}" after one element), the literal
     kernel otherwise.  Every ``NativeEngine`` given the grid must use the same tags."""
     ext = require()
     cls = bool(classes or unicode) and ext.tagset_has_classes(list(tags), bool(classes), bool(unicode), bool(mixed),
-                                                                bool(variants), bool(extended))
+                                                                bool(variants), bool(extended), bool(repeat))
     return ext.HipGrid(device, doors, wg_per_door, idle_ms, classes=cls)
 
 
@@ -129,7 +134,7 @@ class NativeEngine:
     def __init__(self, kind: str, tags: Sequence[str], device: Optional[int] = None,
                  tile_bytes: int = 16384, max_slots: int = 8192, content_cap: int = 1 << 20, lanes: int = 1,
                  grid=None, door: int = -1, ndoors: int = 1, classes: bool = False, unicode: bool = False,
-                 mixed: bool = False, variants: bool = False, extended: bool = False):
+                 mixed: bool = False, variants: bool = False, extended: bool = False, repeat: bool = False):
         ext = require()
         self.kind = kind
         self.name = kind
@@ -139,6 +144,7 @@ class NativeEngine:
         self.mixed = bool(mixed)
         self.variants = bool(variants)
         self.extended = bool(extended)
+        self.repeat = bool(repeat)
         low = sent_tags(tags, classes, unicode, mixed)
         if kind == "hip":
             if ext.device_count() <= 0:
@@ -149,11 +155,11 @@ class NativeEngine:
             # A class tag set needs a grid made with classes=True (make_grid picks the kind)
             self._e = ext.HipEngine(low, device, tile_bytes, max_slots, content_cap, lanes, grid, door, ndoors,
                                      classes=self.classes, unicode=self.unicode, mixed=self.mixed,
-                                     variants=self.variants, extended=self.extended)
+                                     variants=self.variants, extended=self.extended, repeat=self.repeat)
             self.offload = True
         else:
             self._e = ext.CpuEngine(low, classes=self.classes, unicode=self.unicode, mixed=self.mixed,
-                                     variants=self.variants, extended=self.extended)
+                                     variants=self.variants, extended=self.extended, repeat=self.repeat)
             self.offload = False
         self.open = self._e.open
         self.feed = self._e.feed

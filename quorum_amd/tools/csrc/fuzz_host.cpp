@@ -50,6 +50,7 @@ struct ClassSet {
   bool mixed = false;    // a mixed tag set (make_tags' `classes`, `unicode` and `mixed`)
   bool variants = false;  // variable-width tags (make_tags' `variants`, with `classes`)
   bool extended = false;  // shorthands and counted repetition (make_tags' `extended`, with `variants`)
+  bool repeat = false;    // '+', '*' and "{m,}" after one element (make_tags' `repeat`, with `extended`)
 };
 const ClassSet kClassSets[] = {
     {{"think", "th.nk"},
@@ -109,6 +110,25 @@ const ClassSet kClassSets[] = {
       "<\xe6\x80\x9d\\\\d>", "<r\xc3\xa9" "flx>", "</R\xc3\x89" "FLXY>", "<r\xc3\xa9" "fl\xc3\xa9>", "</r\xc3\xa9" "fl\xc3\xa9>",
       "<r\xc3\xa9" "fl\xe6\x80\x9d" "1>", "<r\xc3\xa9" "fl", "x>", "<r\xc3\xa9" "fl >", "<r\xc3\xa9" "fl<>"},
      true, true, true, true},
+    // unbounded repetition: runs inside and beyond the rows, a run up to and past the 61-byte bound,
+    // a non-ASCII digit inside a run (whole and cut inside the code point), a repeated literal
+    {{"step\\d+", "think\\s*", "hm+"},
+     {"<step1>", "</STEP12>", "<step1234>", "<step12345>", "</step12345>", "<step123456789012>", "<step", "12", "345>", ">",
+      "<step>", "<stepx>", "<step1\xd9\xa3" "2>", "</step1\xd9\xa3" "2>", "<step12\xd9", "<step\\\\d+>", "<step\\\\d",
+      "<step12345678901234567890123456789012345678901234567890123456", "7", "8>", "</step1234567890123456789012345678901234567890123456789012345",
+      "67>", "<think>", "<think >", "</THINK \\n\\t  >", "<think      >", "<think\xc2\xa0>", "<think\xe3\x80\x80 >", "<hm>", "</HMMM>",
+      "<hmmmmmmm>", "</hmmmmmmm>", "<hmm", "mm>", "<h>"},
+     false, false, true, true, true},
+    {{"v\\d+\\.\\d+"},
+     {"<v1.2>", "</V12.345>", "<v12345.67890>", "</v12345.67890>", "<v1.>", "<v.1>", "<v1", ".2>", "23", "<v1\xd9\xa3.4>", "<v1.2.3>",
+      "<v1234567890123456789012345678901234567890123456789012345678.", "5", "5>", "<v\\\\d+"},
+     false, false, true, true, true},
+    {{"\xe6\x80\x9d\\d+", "r\xc3\xa9" "fl\\w*", "a{2,}b"},
+     {"<\xe6\x80\x9d" "7>", "</\xe6\x80\x9d" "7>", "<\xe6\x80\x9d" "12345>", "</\xe6\x80\x9d" "12345>", "<\xe6\x80\x9d\xd9\xa3" "1>",
+      "<\xe6\x80\x9d", "12", "345>", "<\xe6\x80\x9d>", "<\xe6\x80\x9d\\\\d+>", "<r\xc3\xa9" "fl>", "</R\xc3\x89" "FLABCDEF>",
+      "<r\xc3\xa9" "fl\xc3\xa9\xe6\x80\x9d_1>", "<r\xc3\xa9" "fl", "abc", "defg>", "<r\xc3\xa9" "fl >",
+      "<aab>", "</AAAAAAB>", "<ab>", "<aa", "ab>", "<aaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaaab>"},
+     true, true, true, true, true},
 };
 const ClassSet* g_class = nullptr;  // the class tag set of this iteration (null: the default tags)
 
@@ -221,7 +241,8 @@ std::string rand_tag() {
   }
   static const char* kAtoms[] = {"a", "b", "t", "(", ")", "(?:", "|", "?", ".", "[0-9]", "[^a]", "[", "]", "\\.", "\\",
                                  "*", "+", "{2}", "é", "思", "<", ">", "/", "^", "$", " ", "X",
-                                 "{", "}", ",", "0", "1", "2", "6", "9", "\\d", "\\w", "\\s", "\\D", "{1,2}", "{,3}"};
+                                 "{", "}", ",", "0", "1", "2", "6", "9", "\\d", "\\w", "\\s", "\\D", "{1,2}", "{,3}",
+                                 "{2,}", "+", "*", "\\d+", "[a-c]*"};
   std::string t;
   const int n = 1 + R(R(4) == 0 ? 70 : 14);
   for (int i = 0; i < n; ++i) t += kAtoms[R(sizeof(kAtoms) / sizeof(kAtoms[0]))];
@@ -234,10 +255,10 @@ bool malformed_tags_hold() {
   std::vector<std::string> tags;
   const int n = 1 + R(3);
   for (int i = 0; i < n; ++i) tags.push_back(rand_tag());
-  const bool unicode = R(2), mixed = R(2), variants = R(4) != 0, extended = R(3) != 0;
+  const bool unicode = R(2), mixed = R(2), variants = R(4) != 0, extended = R(3) != 0, repeat = R(2) != 0;
   try {
-    const Tags t = make_tags(tags, true, unicode, mixed, variants, extended);
-    const auto rows = tagset_rows(tags, true, unicode, mixed, variants, extended);
+    const Tags t = make_tags(tags, true, unicode, mixed, variants, extended, repeat);
+    const auto rows = tagset_rows(tags, true, unicode, mixed, variants, extended, repeat);
     if ((int)rows.size() != t.ts.n || t.ts.n > kMaxTags) return false;
     std::string text = "<" + tags[0] + "></" + tags[0] + "><";
     for (const auto& r : rows) text += "<" + r.first + ">x</" + r.first + ">";
@@ -290,7 +311,8 @@ int main(int argc, char** argv) {
     const Tags tags = make_tags(g_class ? g_class->tags : default_tags,
                                 g_class != nullptr && (!g_class->unicode || g_class->mixed),
                                 g_class != nullptr && g_class->unicode, g_class != nullptr && g_class->mixed,
-                                g_class != nullptr && g_class->variants, g_class != nullptr && g_class->extended);
+                                g_class != nullptr && g_class->variants, g_class != nullptr && g_class->extended,
+                                g_class != nullptr && g_class->repeat);
     int ns = 1 + R(4);
     std::vector<std::string> bodies;
     std::vector<bool> filt;

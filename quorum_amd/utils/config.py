@@ -313,9 +313,18 @@ class RuntimeConfig:
                the native engines — "step\\d", "thought_\\d{1,2}", "h[1-6]{1,2}", "phase\\s\\d".  A
                counted repetition runs as its rows, as '?' does; a non-ASCII character at a
                shorthand position is decided on the host.  \\D, \\W and \\S (the reference's filter
-               and strip disagree about them), "*", "+", "{m,}", lazy and possessive forms, anchors
-               and the other escapes are still refused.  Off (the default): such a tag needs the
-               python engine
+               and strip disagree about them), "*", "+", "{m,}" (without native_repeat_tags), lazy and
+               possessive forms, anchors and the other escapes are still refused.  Off (the default):
+               such a tag needs the python engine
+    native_repeat_tags: with native_regex_tags, native_variant_tags and native_extended_tags all on
+               (refused otherwise), "+", "*" and "{m,}" (m <= 61) after one element — a literal, a
+               bracket class or a shorthand — also run on the native engines: "step\\d+",
+               "thought_\\d+", "think\\s*", "hm+", "v\\d+\\.\\d+".  The repeated element must share no
+               character with what can follow the run ("a\\d+5", "think.*" are refused: there the
+               regex backtracks).  Such a quantifier runs as 4 rows beyond its minimum count, the
+               longest open-ended; a longer run is decided on the host, and a match is at most 61
+               bytes.  A repeat after a group, after a non-ASCII literal and the lazy forms are still
+               refused.  Off (the default): such a tag needs the python engine
     """
 
     engine: str = "auto"
@@ -344,6 +353,7 @@ class RuntimeConfig:
     native_mixed_tags: bool = False
     native_variant_tags: bool = False
     native_extended_tags: bool = False
+    native_repeat_tags: bool = False
 
     def __post_init__(self):
         if not isinstance(self.native_regex_tags, bool):
@@ -364,6 +374,12 @@ class RuntimeConfig:
         if self.native_extended_tags and not (self.native_regex_tags and self.native_variant_tags):
             raise ValueError("runtime.native_extended_tags needs runtime.native_regex_tags and "
                              "runtime.native_variant_tags both true")
+        if not isinstance(self.native_repeat_tags, bool):
+            raise ValueError(f"runtime.native_repeat_tags must be true or false, got {self.native_repeat_tags!r}")
+        if self.native_repeat_tags and not (self.native_regex_tags and self.native_variant_tags
+                                            and self.native_extended_tags):
+            raise ValueError("runtime.native_repeat_tags needs runtime.native_regex_tags, "
+                             "runtime.native_variant_tags and runtime.native_extended_tags all true")
 
     @classmethod
     def from_config(cls, cfg: Dict[str, Any]) -> "RuntimeConfig":

@@ -83,6 +83,10 @@ def main():
     ap.add_argument("--extended", action="store_true",
                     help="with --classes --variants: shorthands and counted repetition (runtime.native_extended_tags), "
                          "e.g. --tags 'step\\d,t\\d?' --body-tag step1 or --tags 'h[1-6]{1,2}' --body-tag h12")
+    ap.add_argument("--repeat", action="store_true",
+                    help="with --classes --variants --extended: '+', '*' and '{m,}' after one element "
+                         "(runtime.native_repeat_tags), e.g. --tags 'think,step\\d+' --body-tag step12 (decided by the rows, "
+                         "on the GPU) or --body-tag step12345 (a run longer than the rows: every stream goes to the host)")
     ap.add_argument("--body-tag", default="think",
                     help="mock shape: the think block's tag as the upstream writes it, e.g. réflexion or RÉFLEXION")
     args = ap.parse_args()
@@ -100,7 +104,7 @@ def main():
         # (so does a pair tag set: --unicode and a cased non-ASCII character in a tag)
         grid = ext.HipGrid(0, args.grid, 8, classes=(args.classes or args.unicode)
                            and ext.tagset_has_classes(tags, args.classes, args.unicode, args.mixed, args.variants,
-                                                      args.extended))
+                                                      args.extended, args.repeat))
     combos = {"ft": (True, True), "f": (True, False), "t": (False, True)}
     for filt, emit in [combos[c] for c in args.combos.split(",")]:
         for n in [int(x) for x in args.slots.split(",")]:
@@ -115,6 +119,8 @@ def main():
                 kw["variants"] = True
             if args.extended:
                 kw["extended"] = True
+            if args.repeat:
+                kw["repeat"] = True
             eng = NativeEngine(args.engine, tags, device=0, max_slots=4096, content_cap=1 << 16, **kw)
             walls = []
             evs = [e + b"\n\n" for e in body.split(b"\n\n") if e]
