@@ -25,8 +25,8 @@ namespace {
 struct PyStreamFilter {
   Tags tags;
   FilterState fs;
-  PyStreamFilter(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat)
-      : tags(make_tags(t, classes, unicode, mixed, variants, extended, repeat)) {}
+  PyStreamFilter(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat, bool runs)
+      : tags(make_tags(t, classes, unicode, mixed, variants, extended, repeat, runs)) {}
   py::bytes feed(const std::string& s) {
     std::string out;
     filter_feed(tags, fs, (const uint8_t*)s.data(), s.size(), out);
@@ -40,8 +40,8 @@ struct PyStreamFilter {
 
 struct PyStripper {
   Tags tags;
-  PyStripper(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat)
-      : tags(make_tags(t, classes, unicode, mixed, variants, extended, repeat)) {}
+  PyStripper(const std::vector<std::string>& t, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat, bool runs)
+      : tags(make_tags(t, classes, unicode, mixed, variants, extended, repeat, runs)) {}
   py::bytes strip(const std::string& s) { return py::bytes(strip_final(tags, (const uint8_t*)s.data(), s.size())); }
 };
 
@@ -145,6 +145,7 @@ ServerCfg server_cfg_from(const py::dict& d) {
   gb("tag_variants", c.tag_variants);
   gb("tag_extended", c.tag_extended);
   gb("tag_repeat", c.tag_repeat);
+  gb("tag_runs", c.tag_runs);
   gs("aggregator_name", c.aggregator_name); gs("prompt_template", c.prompt_template);
   gs("intermediate_separator", c.intermediate_separator); gs("query_format", c.query_format);
   gs("source_label_format", c.source_label_format); gb("include_original_query", c.include_original_query);
@@ -482,39 +483,39 @@ PYBIND11_MODULE(_qmx, m) {
     return py::bytes(out);
   });
   py::class_<PyStreamFilter>(m, "StreamFilter")
-      .def(py::init<const std::vector<std::string>&, bool, bool, bool, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
-           py::arg("unicode") = false, py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false)
+      .def(py::init<const std::vector<std::string>&, bool, bool, bool, bool, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
+           py::arg("unicode") = false, py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::arg("runs") = false)
       .def("feed", &PyStreamFilter::feed)
       .def("flush", &PyStreamFilter::flush);
   py::class_<PyStripper>(m, "Stripper")
-      .def(py::init<const std::vector<std::string>&, bool, bool, bool, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
-           py::arg("unicode") = false, py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false)
+      .def(py::init<const std::vector<std::string>&, bool, bool, bool, bool, bool, bool, bool>(), py::arg("tags"), py::arg("classes") = false,
+           py::arg("unicode") = false, py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::arg("runs") = false)
       .def("strip", &PyStripper::strip);
   // is this tag list inside what make_tags runs natively (the one definition of the subset)?
-  m.def("tagset_ok", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
+  m.def("tagset_ok", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat, bool runs) {
     try {
-      make_tags(tags, classes, unicode, mixed, variants, extended, repeat);
+      make_tags(tags, classes, unicode, mixed, variants, extended, repeat, runs);
       return true;
     } catch (const std::invalid_argument&) {
       return false;
     }
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::arg("runs") = false);
   // why make_tags refuses this tag list ("" when it does not): the limit's own message
-  m.def("tagset_error", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
+  m.def("tagset_error", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat, bool runs) {
     try {
-      make_tags(tags, classes, unicode, mixed, variants, extended, repeat);
+      make_tags(tags, classes, unicode, mixed, variants, extended, repeat, runs);
       return std::string();
     } catch (const std::invalid_argument& e) {
       return std::string(e.what());
     }
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::arg("runs") = false);
   // distinct tags of the set make_tags builds ("É" and "é" are one)
-  m.def("tagset_size", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
-    return make_tags(tags, classes, unicode, mixed, variants, extended, repeat).ts.n;
+  m.def("tagset_size", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat, bool runs) {
+    return make_tags(tags, classes, unicode, mixed, variants, extended, repeat, runs).ts.n;
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::arg("runs") = false);
   // the case rule of one non-ASCII tag character (qmx_unicode_fold.h): (kind, partner) with
   // kind 0 uncased, 1 a simple case pair, 2 refused; partner: the pair's other member, else cp
   m.def("unicode_tag_char", [](uint32_t cp) {
@@ -523,51 +524,141 @@ PYBIND11_MODULE(_qmx, m) {
     return py::make_tuple(kind, kind == 1 ? unicode_tag_partner(cp) : cp);
   });
   // the kind of the tag set this list makes (qmx_text.h TagKind)
-  m.def("tagset_kind", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
-    const TagKind k = make_tags(tags, classes, unicode, mixed, variants, extended, repeat).kind;
+  m.def("tagset_kind", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat, bool runs) {
+    const TagKind k = make_tags(tags, classes, unicode, mixed, variants, extended, repeat, runs).kind;
     return k == TAGS_MIXED ? "mixed" : k == TAGS_PAIR ? "pair" : k == TAGS_CLASS ? "class" : "literal";
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::arg("runs") = false);
   // of the class kind (class, pair or mixed)?  Such a tag set's engines need HipGrid(classes=True)
-  m.def("tagset_has_classes", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
-    return make_tags(tags, classes, unicode, mixed, variants, extended, repeat).kind != TAGS_LITERAL;
+  m.def("tagset_has_classes", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat, bool runs) {
+    return make_tags(tags, classes, unicode, mixed, variants, extended, repeat, runs).kind != TAGS_LITERAL;
   }, py::arg("tags"), py::arg("classes") = true, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::arg("runs") = false);
   // candidates '<' of `text` the GPU kernels would hand to the host path (qmx_text.h
   // class_candidate, the shared suspect rule), with the streaming or the strip tables
   m.def("class_suspects", [](const std::vector<std::string>& tags, const std::string& text, bool strip, bool unicode,
-                             bool mixed, bool variants, bool extended, bool repeat) {
-    const Tags t = make_tags(tags, true, unicode, mixed, variants, extended, repeat);
+                             bool mixed, bool variants, bool extended, bool repeat, bool runs) {
+    const Tags t = make_tags(tags, true, unicode, mixed, variants, extended, repeat, runs);
     int k = 0;
     if (t.kind == TAGS_LITERAL) return k;
     const uint8_t* x = (const uint8_t*)text.data();
     for (int p = 0; p < (int)text.size(); ++p) {
       int tok = 0, len = 0;
       if (x[p] != '<' || t.kind == TAGS_PAIR) continue;  // (a pair tag set has no suspect candidate)
-      const int r = t.kind == TAGS_MIXED ? mixed_candidate(x, (int)text.size(), p, t.ts, t.tc, strip, &tok, &len)
-                                         : class_candidate(x, (int)text.size(), p, t.ts, t.tc, strip, &tok, &len);
-      if (r == CC_SUSPECT) ++k;
+      // (`runs`: the walk with a cursor of its own, as the kernels take it for a set with kVarRuns)
+      if (device_token_at(t.kind, x, (int)text.size(), p, t.ts, t.tc, strip, &tok, &len) == CC_SUSPECT) ++k;
     }
     return k;
   }, py::arg("tags"), py::arg("text"), py::arg("strip") = false, py::arg("unicode") = false, py::arg("mixed") = false,
-     py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
+     py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::arg("runs") = false);
+  // what the GPU kernels decide at every '<' of `text` (qmx_text.h device_token_at, the kernels'
+  // candidate rule compiled for the host): (position, token, length) with token +(row + 1) an open,
+  // -(row + 1) a close, 0 no tag here (length 0), None a suspect candidate: the host path decides
+  m.def("class_candidates", [](const std::vector<std::string>& tags, const std::string& text, bool strip, bool unicode,
+                               bool mixed, bool variants, bool extended, bool repeat, bool runs) {
+    const Tags t = make_tags(tags, true, unicode, mixed, variants, extended, repeat, runs);
+    py::list out;
+    const uint8_t* x = (const uint8_t*)text.data();
+    for (int p = 0; p < (int)text.size(); ++p) {
+      if (x[p] != '<') continue;
+      int tok = 0, len = 0;
+      const int r = device_token_at(t.kind, x, (int)text.size(), p, t.ts, t.tc, strip, &tok, &len);
+      if (r == CC_SUSPECT) out.append(py::make_tuple(p, py::none(), 0));
+      else out.append(py::make_tuple(p, tok, r == CC_MATCH ? len : 0));
+    }
+    return out;
+  }, py::arg("tags"), py::arg("text"), py::arg("strip") = false, py::arg("unicode") = false, py::arg("mixed") = false,
+     py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::arg("runs") = false);
+  // class_candidates against class_matches over every string s of at most `max_len` characters of
+  // `alphabet`, as the text "<s>x</s>": at every '<' the kernels' rule is suspect or answers the
+  // exact walk's token and length.  Counts, and the first few disagreements as
+  // (text, position, (token, length) of the rule, (token, length) of the exact walk).
+  m.def("class_rule_sweep", [](const std::vector<std::string>& tags, const std::string& alphabet, int max_len, bool strip,
+                               bool unicode, bool mixed, bool variants, bool extended, bool repeat, bool runs) {
+    const Tags t = make_tags(tags, true, unicode, mixed, variants, extended, repeat, runs);
+    long long texts = 0, cands = 0, suspects = 0, matches = 0, beyond = 0, nbad = 0;
+    py::list bad;
+    const int na = (int)alphabet.size();
+    std::vector<int> idx;
+    std::string s, text;
+    for (int n = 0; n <= max_len && na > 0; ++n) {
+      idx.assign((size_t)n, 0);
+      while (true) {
+        s.clear();
+        for (int i = 0; i < n; ++i) s += alphabet[(size_t)idx[(size_t)i]];
+        text = "<" + s + ">x</" + s + ">";
+        ++texts;
+        const uint8_t* x = (const uint8_t*)text.data();
+        const int N = (int)text.size();
+        for (int p = 0; p < N; ++p) {
+          if (x[p] != '<') continue;
+          ++cands;
+          int tok = 0, len = 0, wlen = 0;
+          const int r = device_token_at(t.kind, x, N, p, t.ts, t.tc, strip, &tok, &len);
+          if (r == CC_SUSPECT) {
+            ++suspects;
+            continue;
+          }
+          const int want = token_at(t.kind, x, N, p, t.ts, t.tc, strip, &wlen);
+          if (want != 0) {
+            ++matches;
+            const int row = (want < 0 ? -want : want) - 1;
+            if (wlen > t.ts.len[row] + (want < 0 ? 3 : 2)) ++beyond;  // a run longer than its row
+          }
+          if (tok != want || (want != 0 && len != wlen)) {
+            if (++nbad <= 5)
+              bad.append(py::make_tuple(py::bytes(text), p, py::make_tuple(tok, len), py::make_tuple(want, wlen)));
+          }
+        }
+        int k = n - 1;
+        while (k >= 0 && ++idx[(size_t)k] == na) idx[(size_t)k--] = 0;
+        if (k < 0) break;
+      }
+    }
+    py::dict d;
+    d["texts"] = texts;
+    d["candidates"] = cands;
+    d["suspects"] = suspects;
+    d["matches"] = matches;
+    d["beyond_rows"] = beyond;
+    d["mismatched"] = nbad;
+    d["mismatches"] = bad;
+    return d;
+  }, py::arg("tags"), py::arg("alphabet"), py::arg("max_len"), py::arg("strip") = false, py::arg("unicode") = false,
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false,
+     py::arg("runs") = false);
+  // the exact host walk at every '<' of `text` (qmx_text.h token_at): (position, token, length)
+  m.def("class_matches", [](const std::vector<std::string>& tags, const std::string& text, bool strip, bool unicode,
+                            bool mixed, bool variants, bool extended, bool repeat, bool runs) {
+    const Tags t = make_tags(tags, true, unicode, mixed, variants, extended, repeat, runs);
+    py::list out;
+    const uint8_t* x = (const uint8_t*)text.data();
+    for (int p = 0; p < (int)text.size(); ++p) {
+      if (x[p] != '<') continue;
+      int len = 0;
+      const int tok = token_at(t.kind, x, (int)text.size(), p, t.ts, t.tc, strip, &len);
+      out.append(py::make_tuple(p, tok, tok != 0 ? len : 0));
+    }
+    return out;
+  }, py::arg("tags"), py::arg("text"), py::arg("strip") = false, py::arg("unicode") = false, py::arg("mixed") = false,
+     py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::arg("runs") = false);
   // the rows of the set make_tags builds: (row text, index of its tag in `tags`), in order — a
   // variable-width tag (`variants`) has one row per fixed-width expansion, every other tag one
-  m.def("tagset_rows", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
+  m.def("tagset_rows", [](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat, bool runs) {
     py::list out;
-    for (const auto& r : tagset_rows(tags, classes, unicode, mixed, variants, extended, repeat))
+    for (const auto& r : tagset_rows(tags, classes, unicode, mixed, variants, extended, repeat, runs))
       out.append(py::make_tuple(py::bytes(r.first).attr("decode")("utf-8"), r.second));
     return out;
   }, py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false, py::arg("mixed") = false,
-     py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
+     py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::arg("runs") = false);
   env_refresh();
   py::class_<CpuEngine> ce(m, "CpuEngine");
-  ce.def(py::init([](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat) {
+  ce.def(py::init([](const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants, bool extended, bool repeat, bool runs) {
            env_refresh();
-           return new CpuEngine(make_tags(tags, classes, unicode, mixed, variants, extended, repeat));
+           return new CpuEngine(make_tags(tags, classes, unicode, mixed, variants, extended, repeat, runs));
          }),
          py::arg("tags"), py::arg("classes") = false, py::arg("unicode") = false,
-     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false);
+     py::arg("mixed") = false, py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::arg("runs") = false);
   bind_engine(ce);
   // the multi-door grid of loop ticks (tests drive several door engines from Python threads)
   py::class_<HipGrid>(m, "HipGrid")
@@ -613,15 +704,15 @@ PYBIND11_MODULE(_qmx, m) {
   py::class_<HipEngine> he(m, "HipEngine");
   he.def(py::init([](const std::vector<std::string>& tags, int device, int tile, int max_slots, int content_cap,
                       int lanes, HipGrid* grid, int door, int ndoors, bool classes, bool unicode, bool mixed,
-                      bool variants, bool extended, bool repeat) {
+                      bool variants, bool extended, bool repeat, bool runs) {
            env_refresh();
-           return new HipEngine(make_tags(tags, classes, unicode, mixed, variants, extended, repeat), device, tile, max_slots, content_cap, lanes, grid,
+           return new HipEngine(make_tags(tags, classes, unicode, mixed, variants, extended, repeat, runs), device, tile, max_slots, content_cap, lanes, grid,
                                 door, ndoors);
          }),
          py::arg("tags"), py::arg("device"), py::arg("tile_bytes") = 16384, py::arg("max_slots") = 8192,
          py::arg("content_cap") = 1 << 20, py::arg("lanes") = 1, py::arg("grid") = nullptr, py::arg("door") = -1,
          py::arg("ndoors") = 1, py::arg("classes") = false, py::arg("unicode") = false, py::arg("mixed") = false,
-         py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::keep_alive<1, 8>());
+         py::arg("variants") = false, py::arg("extended") = false, py::arg("repeat") = false, py::arg("runs") = false, py::keep_alive<1, 8>());
   bind_engine(he);
   he.def("kernel_stats", &HipEngine::kernel_stats);
   he.def("debug_poison_results", &HipEngine::debug_poison_results, py::arg("ahead") = 1);

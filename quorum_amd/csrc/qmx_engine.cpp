@@ -387,19 +387,19 @@ bool parse_variant_tag(const std::string& t, Rows& out, bool wide, bool extended
 }
 
 Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants,
-                bool extended, bool repeat, std::vector<std::pair<std::string, int>>* rows_out);
+                bool extended, bool repeat, bool runs, std::vector<std::pair<std::string, int>>* rows_out);
 
 }  // namespace
 
 Tags make_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants,
-               bool extended, bool repeat) {
-  return build_tags(tags, classes, unicode, mixed, variants, extended, repeat, nullptr);
+               bool extended, bool repeat, bool runs) {
+  return build_tags(tags, classes, unicode, mixed, variants, extended, repeat, runs, nullptr);
 }
 
 std::vector<std::pair<std::string, int>> tagset_rows(const std::vector<std::string>& tags, bool classes, bool unicode,
-                                                     bool mixed, bool variants, bool extended, bool repeat) {
+                                                     bool mixed, bool variants, bool extended, bool repeat, bool runs) {
   std::vector<std::pair<std::string, int>> rows;
-  build_tags(tags, classes, unicode, mixed, variants, extended, repeat, &rows);
+  build_tags(tags, classes, unicode, mixed, variants, extended, repeat, runs, &rows);
   return rows;
 }
 
@@ -431,11 +431,12 @@ uint32_t unicode_tag_partner(uint32_t cp) {
 
 namespace {
 Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode, bool mixed, bool variants,
-                bool extended, bool repeat, std::vector<std::pair<std::string, int>>* rows_out) {
+                bool extended, bool repeat, bool runs, std::vector<std::pair<std::string, int>>* rows_out) {
   mixed = mixed && classes && unicode;
   variants = variants && classes;
   extended = extended && variants;
   repeat = repeat && extended;
+  runs = runs && repeat;
   Tags out;
   std::memset(&out, 0, sizeof(out));
   TagSet& ts = out.ts;
@@ -624,6 +625,10 @@ Tags build_tags(const std::vector<std::string>& tags, bool classes, bool unicode
     tc.walk = 0;
   }
   if (extended && out.kind == TAGS_CLASS) tc.var |= kVarExtended;
+  // (a set without an open-ended row has no run to walk: its device tables and paths stay what they were)
+  if (runs && (out.kind == TAGS_CLASS || out.kind == TAGS_MIXED))
+    for (int t = 0; t < ts.n; ++t)
+      if (tc.rep[t]) tc.var |= kVarRuns;
   // (a literal tag set keeps no tables: its source text is its names)
   if (out.kind == TAGS_LITERAL) std::memset(&tc, 0, sizeof(tc));
   return out;

@@ -54,14 +54,17 @@ struct Tags {
 // character with what can follow the run.  It expands into kRepeatRows rows beyond its minimum
 // count, the longest of them open-ended at its last copy (TagClasses::rep): the host walks take the
 // rest of the run there, the kernels leave a longer run to the host
+// runs: with repeat, the kernels take a run of ASCII copies past an open-ended row themselves
+// (TagClasses::var, kVarRuns; qmx_text.h WALK_RUNS): the rows, the kind and the host walks are what
+// they are without it
 Tags make_tags(const std::vector<std::string>& tags, bool classes = false, bool unicode = false, bool mixed = false,
-               bool variants = false, bool extended = false, bool repeat = false);
+               bool variants = false, bool extended = false, bool repeat = false, bool runs = false);
 // The rows of the set make_tags builds, in order, as text (a class position as "." or "[]"; an
 // open-ended position — this element, once or more — as the element and a '+'), each with the index
 // of its tag in `tags` (tests, tools/kbench.py)
 std::vector<std::pair<std::string, int>> tagset_rows(const std::vector<std::string>& tags, bool classes = false,
                                                      bool unicode = false, bool mixed = false, bool variants = false,
-                                                     bool extended = false, bool repeat = false);
+                                                     bool extended = false, bool repeat = false, bool runs = false);
 // the case rule of a non-ASCII tag character: 0 uncased, 1 a pair (*lower: its lower member), 2 refused
 int unicode_tag_char(uint32_t cp, uint32_t* lower);
 uint32_t unicode_tag_partner(uint32_t cp);  // the other member of cp's pair (cp: none)

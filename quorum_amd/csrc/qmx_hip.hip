@@ -397,6 +397,23 @@ __device__ inline int tok_plen(const KParams& P, int id) {
   return id > 0 ? P.ts.len[id - 1] + 2 : P.ts.len[-id - 1] + 3;
 }
 
+// The class kernels' block path keeps a byte length per candidate beside cand_tok: a token of a set
+// with kVarRuns is as long as its run, not as its row (0: the pattern's length).  One byte each (a
+// token is at most kMaxTail bytes), laid over chunk_base, which that path first writes after the
+// last hold_cut has read them.
+static_assert(MAX_CAND <= (int)sizeof(Smem::chunk_base), "candidate lengths overlay chunk_base");
+__device__ __forceinline__ uint8_t* cand_lens(Smem& s) { return (uint8_t*)s.chunk_base; }
+__device__ __forceinline__ const uint8_t* cand_lens(const Smem& s) { return (const uint8_t*)s.chunk_base; }
+// the byte length of candidate c's token `id`
+template <bool CLS>
+__device__ __forceinline__ int tok_blen(const Smem& s, const KParams& P, int c, int id) {
+  if constexpr (CLS) {
+    const int len = cand_lens(s)[c];
+    if (len != 0) return len;
+  }
+  return tok_plen(P, id);
+}
+
 // number of tokens with pos < x  /  <= x
 __device__ inline int tok_lower(const Smem& s, int ntok, int x) {
   int lo = 0, hi = ntok;
@@ -492,11 +509,47 @@ __device__ inline int fold_token(const uint8_t* Z, int Zn, int p, const KParams&
 // from one walk (qmx_text.h mixed_candidate), which tells a class marker from a UTF-8 byte by
 // the tag's bitmap.  A match has the pattern's byte length, so the token model holds.  Returns
 // the walk's token (0: none) or kClsSuspect; out of line as the pair walks are.
+// A set with kVarRuns takes the walk with a cursor of its own, and a token it finds is as long as its
+// runs: the walks below hand the byte length back with the token, packed in one int (cand_pack) —
+// 0 where the token is the fast matchers' (`lit`) or there is none: the pattern's length.
+__device__ __forceinline__ int cand_tok(int packed) { return (int16_t)(packed & 0xffff); }
+__device__ __forceinline__ int cand_len(int packed) { return packed >> 16; }
+__device__ __forceinline__ int cand_pack(int r, int tok, int len) {
+  return r == CC_SUSPECT ? kClsSuspect : r == CC_MATCH ? (len << 16) | (tok & 0xffff) : 0;
+}
+// the first in list order of the fast matchers' token and the walk's
+__device__ __forceinline__ int mixed_first(int lit, int tok) {
+  return tok != 0 && (lit == 0 || abs(tok) < abs(lit)) ? tok : lit;
+}
+// (returns the walk's token with its length: cand_pack; a set with kVarRuns takes the walk with a
+// cursor of its own, a function of its own so that this one keeps its registers)
+__device__ __noinline__ int mixed_runs_cand_dev(const uint8_t* x, int n, int p, const TagSet* ts, const TagClasses* tc,
+                                                int strip) {
+  int tok = 0, len = 0;
+  const int r = mixed_candidate<true>(x, n, p, *ts, *tc, strip != 0, &tok, &len);
+  return cand_pack(r, tok, len);
+}
 __device__ __noinline__ int mixed_cand_dev(const uint8_t* x, int n, int p, const TagSet* ts, const TagClasses* tc,
                                            int strip) {
+  if (tc->var & kVarRuns) return mixed_runs_cand_dev(x, n, p, ts, tc, strip);
   int tok = 0, len = 0;
   const int r = mixed_candidate(x, n, p, *ts, *tc, strip != 0, &tok, &len);
-  return r == CC_SUSPECT ? kClsSuspect : r == CC_MATCH ? tok : 0;
+  return cand_pack(r, tok, len);
+}
+// class_candidate for a class set with kVarRuns (an open-ended row whose runs the device decides):
+// one walk per candidate with a cursor of its own, byte-serial over the run — LDS bytes in the tick,
+// global memory in the finalize.  Out of line and entered only for such a set, so the in-line walk
+// of every other class set stays what it is (the class kernels' register budget).
+__device__ __noinline__ int runs_cand_dev(const uint8_t* x, int n, int p, const TagSet* ts, const TagClasses* tc,
+                                          int strip, int lit) {
+  int tok = 0, len = 0;
+  const int r = class_candidate<true>(x, n, p, *ts, *tc, strip != 0, &tok, &len);
+  if (r == CC_MATCH && mixed_first(lit, tok) != tok) return lit & 0xffff;
+  return r == CC_NONE ? lit & 0xffff : cand_pack(r, tok, len);
+}
+// class_prefix for such a set: the run is walked (WALK_RUNS), a tile that ends inside one is held
+__device__ __noinline__ int runs_prefix_dev(const uint8_t* x, int q, int e, const TagSet* ts, const TagClasses* tc) {
+  return class_prefix<WALK_RUNS>(x, q, e, *ts, *tc);
 }
 // class_hold of a mixed tag set: the folded source text outside a block (bit 1 as below), a
 // folded class-aware proper prefix inside one.
@@ -506,24 +559,24 @@ __device__ __noinline__ int mixed_hold_dev(const uint8_t* x, int q, int e, const
     const bool pre = mixed_source_prefix(x, q, e, *ts, *tc);
     return (pre ? 1 : 0) | (tk > 0 && !pre ? 2 : 0);
   }
-  const int r = mixed_prefix(x, q, e, *ts, *tc);
+  const int r = (tc->var & kVarRuns) ? mixed_prefix<WALK_RUNS>(x, q, e, *ts, *tc) : mixed_prefix(x, q, e, *ts, *tc);
   return r == kWalkHost ? 2 : r;  // (a byte >= 0x80 at a class with a shorthand, a run past an open-ended row: the host decides the tile)
 }
-// the first in list order of the fast matchers' token and the walk's
-__device__ __forceinline__ int mixed_first(int lit, int tok) {
-  return tok != 0 && (lit == 0 || abs(tok) < abs(lit)) ? tok : lit;
-}
+// The candidate's token — or kClsSuspect —, and above bit 15 the byte length of a walked token of a
+// set with kVarRuns (cand_tok / cand_len; 0: the pattern's length).
 __device__ __forceinline__ int class_token(const uint8_t* Z, int Zn, int p, const KParams& P, int lit) {
-  if (is_pair_set(*P.cls)) return lit != 0 ? lit : fold_token(Z, Zn, p, P);
+  if (is_pair_set(*P.cls)) return (lit != 0 ? lit : fold_token(Z, Zn, p, P)) & 0xffff;
   if (__builtin_expect(is_mixed_set(*P.cls), 0)) {
-    const int tok = mixed_cand_dev(Z, Zn, p, &P.ts, P.cls, 0);
-    return tok == kClsSuspect ? tok : mixed_first(lit, tok);
+    const int r = mixed_cand_dev(Z, Zn, p, &P.ts, P.cls, 0);
+    if (r == kClsSuspect) return r;
+    return mixed_first(lit, cand_tok(r)) != lit ? r : lit & 0xffff;
   }
+  if (__builtin_expect((P.cls->var & kVarRuns) != 0, 0)) return runs_cand_dev(Z, Zn, p, &P.ts, P.cls, 0, lit);
   int tok = 0, len = 0;
   const int r = class_candidate(Z, Zn, p, P.ts, *P.cls, false, &tok, &len);
   if (r == CC_SUSPECT) return kClsSuspect;
-  if (r == CC_MATCH && (lit == 0 || abs(tok) < abs(lit))) return tok;
-  return lit;
+  if (r == CC_MATCH && (lit == 0 || abs(tok) < abs(lit))) return tok & 0xffff;
+  return lit & 0xffff;
 }
 // The holdback's prefix test for Z[q, e), the last '<' before e that is no completed token
 // (tk: the token that completes later in Z, 0: none; dq: the depth before it).  Outside a
@@ -536,6 +589,10 @@ __device__ __forceinline__ int class_hold(const uint8_t* Z, int q, int e, const 
   if (e - q > kMaxTail) return 0;
   if (is_pair_set(*P.cls)) return fold_prefix_dev(Z, q, e, &P.ts, P.cls, dq == 0);
   if (__builtin_expect(is_mixed_set(*P.cls), 0)) return mixed_hold_dev(Z, q, e, &P.ts, P.cls, dq, tk);
+  if (__builtin_expect(dq != 0 && (P.cls->var & kVarRuns) != 0, 0)) {
+    const int r = runs_prefix_dev(Z, q, e, &P.ts, P.cls);
+    return r == kWalkHost ? 2 : r;  // (what a byte cannot tell in a run: the host decides the tile)
+  }
   if (dq == 0) {
     const bool pre = source_prefix(Z, q, e, P.ts, *P.cls);
     return (pre ? 1 : 0) | (tk > 0 && !pre ? 2 : 0);
@@ -560,7 +617,7 @@ __device__ inline int hold_cut(const Smem& s, const uint8_t* Z, int ncand, int n
   if (idx < 0) return e;
   int q = s.cand[idx];
   int tk = s.cand_tok[idx];
-  if (tk != 0 && q + tok_plen(P, tk) <= e) return e;  // completed token
+  if (tk != 0 && q + tok_blen<CLS>(s, P, idx, tk) <= e) return e;  // completed token
   int dq = s.tok_dep[tok_lower(s, ntok, q)];
   bool pre;
   if constexpr (CLS) {
@@ -2175,6 +2232,7 @@ __device__ __forceinline__ void tick_body(const WorkItem* __restrict__ items, co
         const int r = class_token(Z, Zn, (int)s.cand[c], P, (int)s.cand_tok[c]);
         if (r == kClsSuspect) s.v[V_CLS] = 1;
         else s.cand_tok[c] = (int8_t)r;
+        cand_lens(s)[c] = (uint8_t)cand_len(r);
       }
       __syncthreads();
     }
@@ -2197,7 +2255,7 @@ __device__ __forceinline__ void tick_body(const WorkItem* __restrict__ items, co
         if (id != 0) {
           s.tok_pos[k] = s.cand[lane];
           s.tok_id[k] = (int8_t)id;
-          s.tok_len[k] = (uint8_t)tok_plen(P, id);
+          s.tok_len[k] = (uint8_t)tok_blen<CLS>(s, P, lane, id);
           s.tok_dep[k] = dep16(max(depth0 + ex.x, ex.y));
         }
         if (lane == 63) {
@@ -2229,7 +2287,7 @@ __device__ __forceinline__ void tick_body(const WorkItem* __restrict__ items, co
             int id = s.cand_tok[c];
             s.tok_pos[k] = s.cand[c];
             s.tok_id[k] = (int8_t)id;
-            s.tok_len[k] = (uint8_t)tok_plen(P, id);
+            s.tok_len[k] = (uint8_t)tok_blen<CLS>(s, P, c, id);
           }
         }
         ntok = tot;
@@ -2611,7 +2669,8 @@ struct FinShared {
 };
 enum : int { FV_CUR = 0, FV_PEND, FV_SEGA, FV_NSEG, FV_NTOK, FV_S0, FV_S1, FV_NBIG, FV_OVF,
              FV_CLS,     // class tags: a suspect candidate, or a close that is not its open's captured text
-             FV_PPOS };  // class tags: where the pending open starts
+             FV_PPOS,    // class tags: where the pending open starts
+             FV_PLEN };  // and its byte length (a set with kVarRuns: the length of its name is its own, not the row's)
 
 // match_at of a class tag set for K3 (strip tables: a dot takes a newline): the literal tags
 // by match_at, the class tags by the shared walk, the first in list order wins; kClsSuspect
@@ -2626,14 +2685,20 @@ __device__ __forceinline__ int fin_class_token(const uint8_t* __restrict__ src, 
   if (__builtin_expect(is_mixed_set(tc), 0)) {  // the byte-literal tags by match_at, the others by the one walk
     int lit_len = 0;
     const int lit = match_at(src, n, p, ts, &lit_len);
-    const int tok = mixed_cand_dev(src, n, p, &ts, &tc, 1);
-    if (tok == kClsSuspect) return tok;
-    const int id = mixed_first(lit, tok);
-    if (id != 0) *L = id > 0 ? ts.len[id - 1] + 2 : ts.len[-id - 1] + 3;
+    const int r = mixed_cand_dev(src, n, p, &ts, &tc, 1);
+    if (r == kClsSuspect) return r;
+    const int id = mixed_first(lit, cand_tok(r));
+    if (id != 0) *L = id != lit ? cand_len(r) : lit_len;  // (the walk's length: as long as its runs)
     return id;
   }
   int lit_len = 0, tok = 0, len = 0;
   const int lit = match_at(src, n, p, ts, &lit_len);
+  if (__builtin_expect((tc.var & kVarRuns) != 0, 0)) {
+    const int r = runs_cand_dev(src, n, p, &ts, &tc, 1, lit);
+    if (r == kClsSuspect) return r;
+    *L = cand_len(r) != 0 ? cand_len(r) : lit_len;
+    return cand_tok(r);
+  }
   const int r = class_candidate(src, n, p, ts, tc, true, &tok, &len);
   if (r == CC_SUSPECT) return kClsSuspect;
   if (r == CC_MATCH && (lit == 0 || abs(tok) < abs(lit))) {
@@ -2668,7 +2733,7 @@ __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n
     F.v[FV_SEGA] = 0;
     F.v[FV_NSEG] = 0;
     F.v[FV_OVF] = 0;
-    if constexpr (CLS) F.v[FV_CLS] = F.v[FV_PPOS] = 0;
+    if constexpr (CLS) F.v[FV_CLS] = F.v[FV_PPOS] = F.v[FV_PLEN] = 0;
   }
   auto tok_at = [&](int p, int* L) -> int {
     if constexpr (!CLS) {
@@ -2733,14 +2798,24 @@ __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n
             const int L = __ffsll((unsigned long long)m) - 1;
             if constexpr (CLS) {  // the close's name against the open's captured bytes, a byte per lane
               wave_fence();  // (FV_PPOS: lane 0's store at the open, maybe a window ago)
-              const int ppos = F.v[FV_PPOS], cpos = __shfl(pos, L, 64), nl = ts.len[pend - 1];
+              const int ppos = F.v[FV_PPOS], cpos = __shfl(pos, L, 64);
+              // a set with kVarRuns: the captured name is as long as the open was, and the close's
+              // name must be as long; every byte is compared (one per lane: a name is at most 61),
+              // a non-ASCII literal's by its position alone — two names of one row and one length
+              // that differ, differ at an ASCII byte of one of them
+              const bool runs = (tc->var & kVarRuns) != 0;
+              const int nl = runs ? F.v[FV_PLEN] - 2 : ts.len[pend - 1];
+              const bool nlen = runs && __shfl(end, L, 64) - cpos - 3 != nl;
               // (a pair tag set's tags are literal: open and close of one tag fold to the same bytes;
               // so do the literal characters of a mixed tag set's tags, whose class positions — one
               // ASCII byte each where no candidate is suspect — are the bytes to compare)
-              const bool cmp = is_mixed_set(*tc) ? (tc->clsmask[pend - 1] >> lane) & 1 : !is_pair_set(*tc);
-              const bool ne = lane < nl && cmp &&
-                              lower_ascii(src[ppos + 1 + lane]) != lower_ascii(src[cpos + 2 + lane]);
-              if (__ballot(ne) != 0) {
+              const bool cmp = runs ? true : is_mixed_set(*tc) ? (tc->clsmask[pend - 1] >> lane) & 1 : !is_pair_set(*tc);
+              bool ne = false;
+              if (lane < nl && cmp && !nlen) {
+                const uint8_t a = src[ppos + 1 + lane], b = src[cpos + 2 + lane];
+                ne = lower_ascii(a) != lower_ascii(b) && !(runs && a >= 0x80 && b >= 0x80);
+              }
+              if (nlen || __ballot(ne) != 0) {
                 // (a class set made with the extended language as well: kVarExtended)
                 if (__builtin_expect(is_mixed_set(*tc) || (tc->var & kVarExtended) != 0, 0)) {  // not this open's close: on to the tag's next one
                   cur = cpos + 1;         // (none left: the open stays pending, the host path decides)
@@ -2764,7 +2839,10 @@ __device__ __forceinline__ int fin_select(const uint8_t* __restrict__ src, int n
             pend = __shfl(id, L, 64);
             cur = __shfl(end, L, 64);
             if constexpr (CLS) {
-              if (lane == 0) F.v[FV_PPOS] = po;
+              if (lane == 0) {
+                F.v[FV_PPOS] = po;
+                F.v[FV_PLEN] = cur - po;
+              }
             }
           }
         }

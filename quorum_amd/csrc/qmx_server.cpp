@@ -3703,7 +3703,7 @@ int run_server(const ServerCfg& cfg0) {
   g_ready.store(0);
   // the one tag set of this server: every engine, the verify shadows and the loops share it
   const Tags tags = make_tags(cfg.tags, cfg.tag_classes, cfg.tag_unicode, cfg.tag_mixed, cfg.tag_variants,
-                              cfg.tag_extended, cfg.tag_repeat);
+                              cfg.tag_extended, cfg.tag_repeat, cfg.tag_runs);
   std::vector<std::unique_ptr<Loop>> loops;
   std::vector<std::thread> ts;
   for (int i = 0; i < std::max(1, cfg.threads); ++i) loops.emplace_back(new Loop(cfg, i, tags));

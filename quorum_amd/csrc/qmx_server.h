@@ -64,6 +64,7 @@ struct ServerCfg {
   bool tag_variants = false;  // runtime.native_variant_tags: with tag_classes, tags with '?', '|' and groups run natively
   bool tag_extended = false;  // runtime.native_extended_tags: with tag_variants, the shorthands d, w, s and counted repetition run natively
   bool tag_repeat = false;    // runtime.native_repeat_tags: with tag_extended, '+', '*' and "{m,}" after one element run natively
+  bool tag_runs = false;      // runtime.native_run_tags: with tag_repeat, the GPU decides a run longer than the rows
   // strategy.aggregate (consulted whatever strategy is selected, as in quorum)
   std::string aggregator_name;  // empty = none
   std::string prompt_template, intermediate_separator, query_format, source_label_format;

@@ -99,6 +99,9 @@ struct TagClasses {
   uint64_t rep[kMaxTags];
 };
 constexpr uint32_t kVarRows = 0xffffu, kVarExtended = 1u << 31;
+// kVarRuns (make_tags(..., runs = true), a set with an open-ended row): the device walks take a run
+// of ASCII copies past an open-ended row themselves (WALK_RUNS) instead of leaving it to the host.
+constexpr uint32_t kVarRuns = 1u << 30;
 // Rows an unbounded quantifier expands into beyond its minimum count: `x+` is the counts 4, 3, 2, 1
 // (`x*`: and 0), `x{m,}` m+3 ... m.  Runs up to the longest row's count are decided by the rows (on
 // the GPU); a longer run is decided by the exact host walk.
@@ -219,52 +222,87 @@ QMX_HD int shorthand_char_at(const R& x, int n, int s, uint8_t f, int ln) {  // 
 QMX_HD bool repeat_accepts(const TagClasses& tc, int k, uint8_t c, bool strip) {
   return c < 0x80 ? class_accepts(tc, k, c, strip) : (tc.flags[k] & (CLS_WIDE | CLS_SH)) != 0;
 }
-// The host walks take a run past the row's copies; the device walks never do (kWalkHost), so the
-// byte lengths they see are the rows', bounded by make_tags.
+// How a walk treats the text after the last copy of an open-ended position.
+//   WALK_EXACT: the host walks take the whole run, whatever its characters;
+//   WALK_ROWS:  the device walks of a set without kVarRuns never do (kWalkHost), so the byte lengths
+//               they see are the rows', bounded by make_tags;
+//   WALK_RUNS:  the device walks of a set with kVarRuns take a run of ASCII copies with a cursor of
+//               their own and leave to the host (kWalkHost, a suspect candidate) only what a byte
+//               cannot tell: a byte >= 0x80 where the class holds any, an accepted '<' or '>'.
+// The rule is a template argument, not a matter of which compiler runs: the host compiles WALK_RUNS
+// too (bindings.cpp class_candidates, tools/csrc/fuzz_host.cpp) and wherever it answers it answers as
+// WALK_EXACT does.
+enum : int { WALK_EXACT = 0, WALK_ROWS = 1, WALK_RUNS = 2 };
 #ifdef __HIP_DEVICE_COMPILE__
-constexpr bool kWalkRuns = false;
+constexpr int kWalkRule = WALK_ROWS;
 #else
-constexpr bool kWalkRuns = true;
+constexpr int kWalkRule = WALK_EXACT;
 #endif
-// The run after the copies of an open-ended position of class k, *s the index after the last copy
-// and s0 where the tag's name starts.  Host: consumes while the class accepts the next character
-// (the element's own logic: ASCII table, wide, shorthand ranges).  1: the run ended before a
-// character it does not accept (*s after the run);  -1: the text ended inside the run, or inside
-// a character of it;  0: the name would pass kMaxTagLen bytes — "</" + match + ">" is at most
-// kMaxTail, the holdback's size — which is no match.  Device: 1 where the next byte is not
-// accepted (or the text ended: the caller's proper prefix), kWalkHost where it is.
-// (Out of line, as the mixed walks are: the class kernels keep their register budget —
-// tests/test_isa_class_grid.py — and only a set with an open-ended row comes here.)
+// The run of WALK_RUNS (arguments and answers: repeat_run): ASCII copies other than '<' and '>' are
+// taken; kWalkHost at a byte >= 0x80 the class may hold and at a '<' or '>' it accepts (a class may
+// swallow the next tag's start: token starts are no longer fixed).  In line in the candidate walks,
+// which are out of line themselves (qmx_hip.hip runs_cand_dev, mixed_runs_cand_dev).
 template <class R>
-__attribute__((noinline)) QMX_HD int repeat_run(const R& x, int n, int* s, int s0, const TagClasses& tc, int k, bool strip) {
-#ifdef __HIP_DEVICE_COMPILE__
-  return *s < n && repeat_accepts(tc, k, x[*s], strip) ? kWalkHost : 1;
-#else
+QMX_HD int ascii_run(const R& x, int n, int* s, int s0, const TagClasses& tc, int k, bool strip) {
   const uint8_t f = tc.flags[k];
   int q = *s;
   while (true) {
     if (q >= n) return -1;
     const uint8_t c = x[q];
-    int ln = 1;
-    if (c < 0x80) {
-      if (!class_accepts(tc, k, c, strip)) break;
-    } else {
-      if (!(f & (CLS_WIDE | CLS_SH))) break;
-      ln = utf8_lead_len(c);
-      if (q + ln - s0 > kMaxTagLen) return 0;  // (no follower of such a class takes a byte >= 0x80: no match either way)
-      if (f & CLS_SH) {
-        const int r = shorthand_char_at(x, n, q, f, ln);
-        if (r == 0) break;
-        if (r != 1) return r;
-      }
-      if (q + ln > n) return -1;
+    if (c >= 0x80) {
+      if (f & (CLS_WIDE | CLS_SH)) return kWalkHost;
+      break;
     }
-    if (q + ln - s0 > kMaxTagLen) return 0;
-    q += ln;
+    if (!class_accepts(tc, k, c, strip)) break;
+    if (c == '<' || c == '>') return kWalkHost;
+    if (q + 1 - s0 > kMaxTagLen) return 0;
+    ++q;
   }
   *s = q;
   return 1;
-#endif
+}
+// The run after the copies of an open-ended position of class k, *s the index after the last copy
+// and s0 where the tag's name starts.  Host: consumes while the class accepts the next character
+// (the element's own logic: ASCII table, wide, shorthand ranges).  1: the run ended before a
+// character it does not accept (*s after the run);  -1: the text ended inside the run, or inside
+// a character of it;  0: the name would pass kMaxTagLen bytes — "</" + match + ">" is at most
+// kMaxTail, the holdback's size — which is no match.  WALK_ROWS: 1 where the next byte is not
+// accepted (or the text ended: the caller's proper prefix), kWalkHost where it is.  WALK_RUNS:
+// ascii_run, the host's answers over ASCII copies.
+// (Out of line, as the mixed walks are: the class kernels keep their register budget —
+// tests/test_isa_class_grid.py — and only a set with an open-ended row comes here.)
+template <int W = kWalkRule, class R>
+__attribute__((noinline)) QMX_HD int repeat_run(const R& x, int n, int* s, int s0, const TagClasses& tc, int k, bool strip) {
+  if constexpr (W == WALK_ROWS) {
+    return *s < n && repeat_accepts(tc, k, x[*s], strip) ? kWalkHost : 1;
+  } else if constexpr (W == WALK_RUNS) {
+    return ascii_run(x, n, s, s0, tc, k, strip);
+  } else {
+    const uint8_t f = tc.flags[k];
+    int q = *s;
+    while (true) {
+      if (q >= n) return -1;
+      const uint8_t c = x[q];
+      int ln = 1;
+      if (c < 0x80) {
+        if (!class_accepts(tc, k, c, strip)) break;
+      } else {
+        if (!(f & (CLS_WIDE | CLS_SH))) break;
+        ln = utf8_lead_len(c);
+        if (q + ln - s0 > kMaxTagLen) return 0;  // (no follower of such a class takes a byte >= 0x80: no match either way)
+        if (f & CLS_SH) {
+          const int r = shorthand_char_at(x, n, q, f, ln);
+          if (r == 0) break;
+          if (r != 1) return r;
+        }
+        if (q + ln > n) return -1;
+      }
+      if (q + ln - s0 > kMaxTagLen) return 0;
+      q += ln;
+    }
+    *s = q;
+    return 1;
+  }
 }
 
 // Walk pattern `pat` (pat < n: "<t>", else "</t>") over x[p:n).  1: it matches, *end is the
@@ -272,7 +310,7 @@ __attribute__((noinline)) QMX_HD int repeat_run(const R& x, int n, int* s, int s
 // before the pattern did (a proper prefix — a code point cut short at n counts as one);
 // kWalkHost: device code met a byte >= 0x80 at a class with a shorthand (shorthand_char_at), or one
 // more copy after an open-ended position (repeat_run).
-template <class R>
+template <int W = kWalkRule, class R>
 QMX_HD int class_walk(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, int pat, bool strip,
                       int* end) {
   const bool close = pat >= ts.n;
@@ -286,6 +324,7 @@ QMX_HD int class_walk(const R& x, int n, int p, const TagSet& ts, const TagClass
     if (x[s] != '/') return 0;
     ++s;
   }
+  constexpr bool kWalkRuns = W != WALK_ROWS;
   const int s0 = s;     // the name starts here; opened: a run was taken, so its length is no longer the row's
   bool opened = false;
   for (int i = 0; i < ts.len[t]; ++i) {
@@ -306,14 +345,18 @@ QMX_HD int class_walk(const R& x, int n, int p, const TagSet& ts, const TagClass
       const int ln = c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : c >= 0xC0 ? 2 : 1;
       if (kWalkRuns && opened && s + ln - s0 > kMaxTagLen) return 0;
       if (f & CLS_SH) {
-        const int r = shorthand_char_at(x, n, s, f, ln);
-        if (r != 1) return r;
+        if constexpr (W != WALK_EXACT) {
+          return kWalkHost;  // (the tables of \d, \w and \s are host data)
+        } else {
+          const int r = shorthand_char_at(x, n, s, f, ln);
+          if (r != 1) return r;
+        }
       }
       if (s + ln > n) return -1;
       s += ln;
     }
     if (__builtin_expect((tc.rep[t] >> i) & 1, 0)) {
-      const int r = repeat_run(x, n, &s, s0, tc, e - 0x80, strip);
+      const int r = repeat_run<W>(x, n, &s, s0, tc, e - 0x80, strip);
       if (r != 1) return r;
       opened = true;
     }
@@ -373,7 +416,21 @@ __attribute__((noinline)) QMX_HD bool repeat_suspect(const R& x, int n, int q, c
   if (((tc.rep[t] >> i) & 1) == 0) return false;
   return q < n && repeat_accepts(tc, k, x[q], strip);
 }
+// The run of a candidate walk (RUNS: a set with kVarRuns, the rule of WALK_RUNS): position i of row
+// t, of class k, has matched at x[*s - 1].  Where it is open-ended the cursor moves over the ASCII
+// copies that follow.  CC_NONE: go on at *s (no open-ended position, or the run ended before a byte
+// the class does not accept);  CC_SUSPECT: a byte >= 0x80 the class may hold, or a '<' or '>' it
+// accepts;  CC_MATCH — read as "mismatch of the row" —: the text ended inside the run, or the name
+// would pass kMaxTagLen bytes.
 template <class R>
+QMX_HD int candidate_run(const R& x, int n, int* s, int s0, const TagClasses& tc, int t, int i, int k, bool strip) {
+  if (((tc.rep[t] >> i) & 1) == 0) return CC_NONE;
+  const int r = ascii_run(x, n, s, s0, tc, k, strip);
+  return r == 1 ? CC_NONE : r == kWalkHost ? CC_SUSPECT : CC_MATCH;
+}
+// RUNS: the walk has a cursor of its own, s, which a run moves past the row's position (s0 + i
+// without one); a match's length is the row's plus the extra copies of all its runs.
+template <bool RUNS = false, class R>
 QMX_HD int class_candidate(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, bool strip, int* tok,
                            int* tok_len) {
   const bool close = p + 1 < n && x[p + 1] == '/';
@@ -385,25 +442,39 @@ QMX_HD int class_candidate(const R& x, int n, int p, const TagSet& ts, const Tag
       for (int i = 0; i < L; ++i) has = has || ts.name[t][i] >= 0x80;
     if (!has) continue;
     bool ok = true;
+    int s = s0;  // (RUNS only: the text position of row position i)
       for (int i = 0; ok && i < L; ++i) {
-      if (s0 + i >= n) {
+      if constexpr (!RUNS) s = s0 + i;
+      if (s >= n || (RUNS && s - s0 >= kMaxTagLen)) {
         ok = false;
         break;
       }
-      const uint8_t c = x[s0 + i], e = ts.name[t][i];
+      const uint8_t c = x[s], e = ts.name[t][i];
       if (e < 0x80) ok = lower_ascii(c) == e;
       else if (c == '<' || c == '>' || c >= 0x80) {
         if (!variant_mismatch(tc, e - 0x80, c)) return CC_SUSPECT;
         ok = false;
       } else {
         ok = class_accepts(tc, e - 0x80, c, strip);
-        if (ok && repeat_suspect(x, n, s0 + i + 1, tc, t, i, e - 0x80, strip)) return CC_SUSPECT;
+        if constexpr (RUNS) {
+          if (ok) {
+            ++s;
+            const int r = candidate_run(x, n, &s, s0, tc, t, i, e - 0x80, strip);
+            if (r == CC_SUSPECT) return CC_SUSPECT;
+            ok = r == CC_NONE;
+            continue;
+          }
+        } else {
+          if (ok && repeat_suspect(x, n, s0 + i + 1, tc, t, i, e - 0x80, strip)) return CC_SUSPECT;
+        }
       }
+      if constexpr (RUNS) ++s;
     }
-    if (ok && res == CC_NONE && s0 + L < n && x[s0 + L] == '>') {
+    if constexpr (!RUNS) s = s0 + L;
+    if (ok && res == CC_NONE && s < n && x[s] == '>') {
       res = CC_MATCH;
       *tok = close ? -(t + 1) : (t + 1);
-      *tok_len = s0 + L + 1 - p;
+      *tok_len = s + 1 - p;
     }
   }
   return res;
@@ -411,12 +482,12 @@ QMX_HD int class_candidate(const R& x, int n, int p, const TagSet& ts, const Tag
 
 // Is x[q:n) a proper class-aware prefix of some open or close pattern (streaming tables)?
 // 1: yes, 0: no, kWalkHost: some walk could not tell on the device (never on the host).
-template <class R>
+template <int W = kWalkRule, class R>
 QMX_HD int class_prefix(const R& x, int q, int n, const TagSet& ts, const TagClasses& tc) {
   int res = 0;
   for (int pat = 0; pat < 2 * ts.n; ++pat) {
     int end = 0;
-    const int r = class_walk(x, n, q, ts, tc, pat, false, &end);
+    const int r = class_walk<W>(x, n, q, ts, tc, pat, false, &end);
     if (r == -1) return 1;  // (held: the next tile's candidate meets what a later pattern could not tell)
     if (r == kWalkHost) res = kWalkHost;
   }
@@ -529,7 +600,7 @@ QMX_HD int fold_char_at(const R& x, int n, int s, uint32_t want, int ln, const T
 }
 // class_walk for a mixed tag set: a class position is one the tag's bitmap names, every other
 // byte >= 0x80 of name[] starts or continues a literal character, compared with the text folded.
-template <class R>
+template <int W = kWalkRule, class R>
 QMX_HD int mixed_walk(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, int pat, bool strip,
                       int* end) {
   const bool close = pat >= ts.n;
@@ -544,6 +615,7 @@ QMX_HD int mixed_walk(const R& x, int n, int p, const TagSet& ts, const TagClass
     if (x[s] != '/') return 0;
     ++s;
   }
+  constexpr bool kWalkRuns = W != WALK_ROWS;
   const int s0 = s;  // (as in class_walk)
   bool opened = false;
   for (int i = 0; i < ts.len[t];) {
@@ -561,14 +633,18 @@ QMX_HD int mixed_walk(const R& x, int n, int p, const TagSet& ts, const TagClass
         const int ln = utf8_lead_len(c);
         if (kWalkRuns && opened && s + ln - s0 > kMaxTagLen) return 0;
         if (f & CLS_SH) {
-          const int r = shorthand_char_at(x, n, s, f, ln);
-          if (r != 1) return r;
+          if constexpr (W != WALK_EXACT) {
+            return kWalkHost;
+          } else {
+            const int r = shorthand_char_at(x, n, s, f, ln);
+            if (r != 1) return r;
+          }
         }
         if (s + ln > n) return -1;
         s += ln;
       }
       if (__builtin_expect((tc.rep[t] >> i) & 1, 0)) {
-        const int r = repeat_run(x, n, &s, s0, tc, k, strip);
+        const int r = repeat_run<W>(x, n, &s, s0, tc, k, strip);
         if (r != 1) return r;
         opened = true;
       }
@@ -615,7 +691,8 @@ QMX_HD int mixed_match_at(const R& x, int n, int p, const TagSet& ts, const TagC
 // compare, a non-ASCII literal by its folded bytes (never suspect), a class position by its
 // ASCII table; '<', '>' or a byte >= 0x80 AT a class position makes the candidate suspect.  A
 // match has the pattern's byte length.
-template <class R>
+// (RUNS: as class_candidate — a cursor of its own, the match's length the walk's.)
+template <bool RUNS = false, class R>
 QMX_HD int mixed_candidate(const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, bool strip, int* tok,
                            int* tok_len) {
   const bool close = p + 1 < n && x[p + 1] == '/';
@@ -626,48 +703,66 @@ QMX_HD int mixed_candidate(const R& x, int n, int p, const TagSet& ts, const Tag
     const int L = ts.len[t];
     const uint64_t cm = tc.clsmask[t];
     bool ok = true;
+    int s = s0;  // (RUNS only: the text position of name byte i)
     for (int i = 0; ok && i < L;) {
-      if (s0 + i >= n) {
+      if constexpr (!RUNS) s = s0 + i;
+      if (s >= n || (RUNS && s - s0 >= kMaxTagLen)) {
         ok = false;
         break;
       }
-      const uint8_t c = x[s0 + i], e = ts.name[t][i];
+      const uint8_t c = x[s], e = ts.name[t][i];
       if ((cm >> i) & 1) {
         if (c == '<' || c == '>' || c >= 0x80) {
           if (!variant_mismatch(tc, e - 0x80, c)) return CC_SUSPECT;
           ok = false;
         } else {
           ok = class_accepts(tc, e - 0x80, c, strip);
-          if (ok && repeat_suspect(x, n, s0 + i + 1, tc, t, i, e - 0x80, strip)) return CC_SUSPECT;
+          if constexpr (RUNS) {
+            ++s;
+            if (ok) {
+              const int r = candidate_run(x, n, &s, s0, tc, t, i, e - 0x80, strip);
+              if (r == CC_SUSPECT) return CC_SUSPECT;
+              ok = r == CC_NONE;
+            }
+          } else {
+            if (ok && repeat_suspect(x, n, s0 + i + 1, tc, t, i, e - 0x80, strip)) return CC_SUSPECT;
+          }
         }
         ++i;
       } else if (e < 0x80) {
         ok = lower_ascii(c) == e;
         ++i;
+        if constexpr (RUNS) ++s;
       } else {
         const int ln = utf8_lead_len(e);
+        if (RUNS && s + ln - s0 > kMaxTagLen) {
+          ok = false;
+          break;
+        }
         uint32_t want = 0;
         for (int k = 0; k < ln; ++k) want |= (uint32_t)ts.name[t][i + k] << (8 * k);
-        ok = fold_char_at(x, n, s0 + i, want, ln, tc) == 1;
+        ok = fold_char_at(x, n, s, want, ln, tc) == 1;
         i += ln;
+        if constexpr (RUNS) s += ln;
       }
     }
-    if (ok && res == CC_NONE && s0 + L < n && x[s0 + L] == '>') {
+    if constexpr (!RUNS) s = s0 + L;
+    if (ok && res == CC_NONE && s < n && x[s] == '>') {
       res = CC_MATCH;
       *tok = close ? -(t + 1) : (t + 1);
-      *tok_len = s0 + L + 1 - p;
+      *tok_len = s + 1 - p;
     }
   }
   return res;
 }
 
 // class_prefix for a mixed tag set
-template <class R>
+template <int W = kWalkRule, class R>
 QMX_HD int mixed_prefix(const R& x, int q, int n, const TagSet& ts, const TagClasses& tc) {
   int res = 0;
   for (int pat = 0; pat < 2 * ts.n; ++pat) {
     int end = 0;
-    const int r = mixed_walk(x, n, q, ts, tc, pat, false, &end);
+    const int r = mixed_walk<W>(x, n, q, ts, tc, pat, false, &end);
     if (r == -1) return 1;
     if (r == kWalkHost) res = kWalkHost;
   }
@@ -712,6 +807,38 @@ QMX_HD int token_at(TagKind kind, const R& x, int n, int p, const TagSet& ts, co
        : kind == TAGS_PAIR  ? fold_match_at(x, n, p, ts, tc, tok_len)
        : kind == TAGS_MIXED ? mixed_match_at(x, n, p, ts, tc, strip, tok_len)
                             : match_at(x, n, p, ts, tok_len);
+}
+
+// What the GPU kernels decide at the candidate '<' at p, on the host (qmx_hip.hip class_token and
+// fin_class_token): the byte matchers' token for the rows without a class element or a pair
+// character, the candidate walk's for the others — with a cursor of its own where the set has
+// kVarRuns —, the first of the two in list order.  CC_MATCH (*tok, *tok_len), CC_NONE: no tag here,
+// CC_SUSPECT: the kernels hand the stream to the host path.
+template <class R>
+inline int device_token_at(TagKind kind, const R& x, int n, int p, const TagSet& ts, const TagClasses& tc, bool strip,
+                           int* tok, int* tok_len) {
+  *tok = 0;
+  if (kind == TAGS_PAIR || kind == TAGS_LITERAL) {
+    *tok = token_at(kind, x, n, p, ts, tc, strip, tok_len);
+    return *tok != 0 ? CC_MATCH : CC_NONE;
+  }
+  int lit_len = 0, wtok = 0, wlen = 0;
+  const int lit = match_at(x, n, p, ts, &lit_len);
+  const bool runs = (tc.var & kVarRuns) != 0;
+  const int r = kind == TAGS_MIXED ? (runs ? mixed_candidate<true>(x, n, p, ts, tc, strip, &wtok, &wlen)
+                                           : mixed_candidate(x, n, p, ts, tc, strip, &wtok, &wlen))
+                                   : (runs ? class_candidate<true>(x, n, p, ts, tc, strip, &wtok, &wlen)
+                                           : class_candidate(x, n, p, ts, tc, strip, &wtok, &wlen));
+  if (r == CC_SUSPECT) return CC_SUSPECT;
+  const int a = wtok < 0 ? -wtok : wtok, b = lit < 0 ? -lit : lit;
+  if (r == CC_MATCH && (lit == 0 || a < b)) {
+    *tok = wtok;
+    *tok_len = wlen;
+  } else if (lit != 0) {
+    *tok = lit;
+    *tok_len = lit_len;
+  }
+  return *tok != 0 ? CC_MATCH : CC_NONE;
 }
 
 // Is x[q:n), the text from the last '<', held back at depth `depth`?  A class tag set holds the

@@ -70,7 +70,7 @@ def _unicode_tag_chars_ok(tags: Sequence[str]) -> bool:
 
 def native_tag_ok(tags: Sequence[str], max_tags: int = 16, max_len: int = 61, classes: bool = False,
                   unicode: bool = False, mixed: bool = False, variants: bool = False,
-                  extended: bool = False, repeat: bool = False) -> bool:
+                  extended: bool = False, repeat: bool = False, runs: bool = False) -> bool:
     """Tags the native/GPU matchers run exactly (qmx_text.h): literal printable ASCII, at
     most 16 distinct (lowercased) tags of at most 61 bytes — the MFMA matcher compares a
     16-byte window per '<' and the tail of longer patterns, two 16-pattern column blocks.
@@ -94,7 +94,10 @@ def native_tag_ok(tags: Sequence[str], max_tags: int = 16, max_len: int = 61, cl
     ``\\w`` and ``\\s`` and counted repetition ``{m}``, ``{m,n}``, ``{,n}`` ("step\\d", "h[1-6]{1,2}").
 
     ``repeat`` (``runtime.native_repeat_tags``, with ``extended``): also ``+``, ``*`` and ``{m,}`` after
-    one element whose class shares no character with what can follow the run ("step\\d+", "think\\s*")."""
+    one element whose class shares no character with what can follow the run ("step\\d+", "think\\s*").
+
+    ``runs`` (``runtime.native_run_tags``, with ``repeat``): the GPU decides a run longer than the rows; what
+    runs natively is the same."""
     low = {t.lower() for t in tags}
     if (0 < len(low) <= max_tags
             and all(_PLAIN_TAG.match(t) and not (set(t) & _NOT_PLAIN) and len(t) <= max_len for t in low)):
@@ -102,6 +105,7 @@ def native_tag_ok(tags: Sequence[str], max_tags: int = 16, max_len: int = 61, cl
     variants = bool(variants and classes)
     extended = bool(extended and variants)
     repeat = bool(repeat and extended)
+    runs = bool(runs and repeat)
     if not (classes or unicode) or max_tags != 16 or max_len != 61:
         return False
     if unicode and not _unicode_tag_chars_ok([str(t) for t in tags]):
@@ -109,7 +113,7 @@ def native_tag_ok(tags: Sequence[str], max_tags: int = 16, max_len: int = 61, cl
     from . import native
 
     return native.available() and bool(native.require().tagset_ok([str(t) for t in tags], bool(classes),
-                                                                  bool(unicode), bool(mixed), variants, extended, repeat))
+                                                                  bool(unicode), bool(mixed), variants, extended, repeat, runs))
 
 
 class PyEngine:
@@ -216,7 +220,7 @@ def make_engine(kind: str, tags: Sequence[str], device: Optional[int] = None, **
     extension or a GPU is missing (no silent fallback on a GPU box).  ``opts`` go to the
     native engine as they are; a ``grid`` among them must be of the tag set's kind
     (``native.make_grid(tags, ..., classes=classes, unicode=unicode, mixed=mixed,
-    variants=variants, extended=extended, repeat=repeat)``: the class grid for a class, a pair and a mixed tag set
+    variants=variants, extended=extended, repeat=repeat, runs=runs)``: the class grid for a class, a pair and a mixed tag set
     and for a set with a variable-width tag).
     """
     tags = list(tags)
@@ -226,8 +230,9 @@ def make_engine(kind: str, tags: Sequence[str], device: Optional[int] = None, **
     variants = bool(opts.pop("variants", False)) and classes
     extended = bool(opts.pop("extended", False)) and variants
     repeat = bool(opts.pop("repeat", False)) and extended
+    runs = bool(opts.pop("runs", False)) and repeat
     ok = native_tag_ok(tags, classes=classes, unicode=unicode, mixed=mixed, variants=variants, extended=extended,
-                       repeat=repeat)
+                       repeat=repeat, runs=runs)
     if kind == "python" or not ok:
         if kind in ("hip", "cpu") and not ok:
             logger.warning("thinking_tags %r need regex semantics: using the python engine", tags)
@@ -240,7 +245,8 @@ def make_engine(kind: str, tags: Sequence[str], device: Optional[int] = None, **
             return _py_engine(tags)
         kind = "hip" if native.gpu_available() else "cpu"
     # (the tags as they reach the extension: "[Z-a]" and "[z-a]" are different patterns)
-    key = ((kind, classes, unicode, mixed, variants, extended, repeat) if repeat
+    key = ((kind, classes, unicode, mixed, variants, extended, repeat, runs) if runs
+           else (kind, classes, unicode, mixed, variants, extended, repeat) if repeat
            else (kind, classes, unicode, mixed, variants, extended) if extended
            else (kind, classes, unicode, mixed, variants) if variants
            else (kind, classes, unicode, mixed) if mixed else (kind, classes, unicode) if classes or unicode else kind,
@@ -257,6 +263,8 @@ def make_engine(kind: str, tags: Sequence[str], device: Optional[int] = None, **
             opts["extended"] = True
         if repeat:
             opts["repeat"] = True
+        if runs:
+            opts["runs"] = True
         eng = native.NativeEngine(kind, tags, device=device, classes=classes, **opts)
         _NATIVE_CACHE[key] = eng
     return eng

@@ -52,21 +52,22 @@ def gpu_available() -> bool:
 
 
 def sent_tags(tags: Sequence[str], classes: bool = False, unicode: bool = False, mixed: bool = False,
-              variants: bool = False, extended: bool = False, repeat: bool = False) -> List[str]:
+              variants: bool = False, extended: bool = False, repeat: bool = False, runs: bool = False) -> List[str]:
     """The tag list as it is sent to the extension, first occurrence only.  Class and non-ASCII
     tags go down as written (lowercasing would turn "[Z-a]" into another pattern; the C++ parser
     folds non-ASCII tags through its pair table), plain tags through ``str.lower()``, which is
     more than ASCII lowercasing: "THIN\u212a" (Kelvin sign) is "think" and runs; as written it would not.
     (``mixed`` needs both other keys, ``variants`` needs ``classes``, ``extended`` needs ``variants``
-    and ``repeat`` needs ``extended``, so they change nothing here.)"""
+    and ``repeat`` needs ``extended``, so they change nothing here; neither does ``runs``, which changes only
+    what the GPU decides.)"""
     return list(dict.fromkeys(t if classes or unicode or mixed else t.lower() for t in tags))
 
 
 def strip_fn(tags: Sequence[str], classes: bool = False, unicode: bool = False,
-             mixed: bool = False, variants: bool = False, extended: bool = False, repeat: bool = False) -> Callable[[str, bool], str]:
+             mixed: bool = False, variants: bool = False, extended: bool = False, repeat: bool = False, runs: bool = False) -> Callable[[str, bool], str]:
     ext = require()
     stripper = ext.Stripper(sent_tags(tags, classes, unicode, mixed), classes=bool(classes), unicode=bool(unicode),
-                            mixed=bool(mixed), variants=bool(variants), extended=bool(extended), repeat=bool(repeat))
+                            mixed=bool(mixed), variants=bool(variants), extended=bool(extended), repeat=bool(repeat), runs=bool(runs))
 
     def _strip(text, on):
         if not on:
@@ -79,7 +80,7 @@ def strip_fn(tags: Sequence[str], classes: bool = False, unicode: bool = False,
 
 
 def tagset_rows(tags: Sequence[str], classes: bool = False, unicode: bool = False, mixed: bool = False,
-                variants: bool = False, extended: bool = False, repeat: bool = False) -> List[tuple]:
+                variants: bool = False, extended: bool = False, repeat: bool = False, runs: bool = False) -> List[tuple]:
     """The rows of the tag set the extension builds from ``tags``: ``(row text, index of its tag)``
     in matching order.  A variable-width tag (``variants``) has one row per fixed-width expansion
     in the regex's priority order ("think(ing)?": "thinking", "think"); every other tag has one.
@@ -87,44 +88,74 @@ def tagset_rows(tags: Sequence[str], classes: bool = False, unicode: bool = Fals
     and the longest is open-ended: its last copy is written with a ``+`` after it and stands for
     "this element, once or more" ("step\\d+": "step\\d\\d\\d\\d+", "step\\d\\d\\d", "step\\d\\d", "step\\d")."""
     return [(str(r), int(i)) for r, i in require().tagset_rows([str(t) for t in tags], bool(classes), bool(unicode),
-                                                               bool(mixed), bool(variants), bool(extended), bool(repeat))]
+                                                               bool(mixed), bool(variants), bool(extended), bool(repeat), bool(runs))]
 
 
 def tagset_ok(tags: Sequence[str], classes: bool = False, unicode: bool = False, mixed: bool = False,
-              variants: bool = False, extended: bool = False, repeat: bool = False) -> bool:
+              variants: bool = False, extended: bool = False, repeat: bool = False, runs: bool = False) -> bool:
     """Does the extension run this tag list natively (``make_tags`` is the one definition)?"""
     return bool(require().tagset_ok([str(t) for t in tags], bool(classes), bool(unicode), bool(mixed),
-                                    bool(variants), bool(extended), bool(repeat)))
+                                    bool(variants), bool(extended), bool(repeat), bool(runs)))
 
 
 def tagset_kind(tags: Sequence[str], classes: bool = False, unicode: bool = False, mixed: bool = False,
-                variants: bool = False, extended: bool = False, repeat: bool = False) -> str:
+                variants: bool = False, extended: bool = False, repeat: bool = False, runs: bool = False) -> str:
     """"literal", "class", "pair" or "mixed": the kind of the tag set this list makes."""
     return str(require().tagset_kind([str(t) for t in tags], bool(classes), bool(unicode), bool(mixed),
-                                     bool(variants), bool(extended), bool(repeat)))
+                                     bool(variants), bool(extended), bool(repeat), bool(runs)))
 
 
 def class_suspects(tags: Sequence[str], text: bytes, strip: bool = False, unicode: bool = False,
-                   mixed: bool = False, variants: bool = False, extended: bool = False, repeat: bool = False) -> int:
-    """Candidates '<' of ``text`` the GPU kernels would hand to the host path."""
+                   mixed: bool = False, variants: bool = False, extended: bool = False, repeat: bool = False, runs: bool = False) -> int:
+    """Candidates '<' of ``text`` the GPU kernels would hand to the host path (``runs``: by the rule of
+    ``runtime.native_run_tags``, which walks a run of ASCII copies past an open-ended row)."""
     return int(require().class_suspects([str(t) for t in tags], bytes(text), bool(strip), bool(unicode),
-                                        bool(mixed), bool(variants), bool(extended), bool(repeat)))
+                                        bool(mixed), bool(variants), bool(extended), bool(repeat), bool(runs)))
+
+
+def class_candidates(tags: Sequence[str], text: bytes, strip: bool = False, unicode: bool = False,
+                     mixed: bool = False, variants: bool = False, extended: bool = False, repeat: bool = False,
+                     runs: bool = False) -> List[tuple]:
+    """What the GPU kernels decide at every '<' of ``text``, computed on the host by the kernels' own
+    candidate rule: ``(position, token, length)`` with token ``+(row + 1)`` an open, ``-(row + 1)`` a
+    close, ``0`` no tag here and ``None`` a suspect candidate, which the host path decides."""
+    return [tuple(c) for c in require().class_candidates([str(t) for t in tags], bytes(text), bool(strip), bool(unicode),
+                                                         bool(mixed), bool(variants), bool(extended), bool(repeat), bool(runs))]
+
+
+def class_rule_sweep(tags: Sequence[str], alphabet: bytes, max_len: int, strip: bool = False, unicode: bool = False,
+                     mixed: bool = False, variants: bool = False, extended: bool = False, repeat: bool = False,
+                     runs: bool = False) -> dict:
+    """``class_candidates`` against ``class_matches`` at every '<' of ``"<s>x</s>"`` for every string ``s`` of
+    at most ``max_len`` bytes of ``alphabet``, enumerated in the extension: the counts ``texts``,
+    ``candidates``, ``suspects``, ``matches``, ``beyond_rows`` (matches longer than their row),
+    ``mismatched`` and the first few ``mismatches``."""
+    return dict(require().class_rule_sweep([str(t) for t in tags], bytes(alphabet), int(max_len), bool(strip), bool(unicode),
+                                           bool(mixed), bool(variants), bool(extended), bool(repeat), bool(runs)))
+
+
+def class_matches(tags: Sequence[str], text: bytes, strip: bool = False, unicode: bool = False,
+                  mixed: bool = False, variants: bool = False, extended: bool = False, repeat: bool = False,
+                  runs: bool = False) -> List[tuple]:
+    """The exact host walk's ``(position, token, length)`` at every '<' of ``text`` (token 0: none)."""
+    return [tuple(c) for c in require().class_matches([str(t) for t in tags], bytes(text), bool(strip), bool(unicode),
+                                                      bool(mixed), bool(variants), bool(extended), bool(repeat), bool(runs))]
 
 
 def make_grid(tags: Sequence[str], device: int, doors: int, wg_per_door: int = 8, idle_ms: int = 50,
               classes: bool = False, unicode: bool = False, mixed: bool = False, variants: bool = False, extended: bool = False,
-              repeat: bool = False):
+              repeat: bool = False, runs: bool = False):
     """A multi-door loop-tick grid (``HipGrid``) of the kind this tag set's engines need: the
     class kernel for a class tag set (``classes`` on and a '.' or bracket class in a tag), for
     a pair tag set (``unicode`` on and a cased non-ASCII character in a tag) and for a mixed tag
     set (``mixed`` on with both, class elements and non-ASCII literals in one set) and for a set
     with a variable-width tag (``variants`` on with ``classes``: '?', '|', groups; ``extended`` on
     with ``variants``: shorthands and counted repetition; ``repeat`` on with ``extended``: '+', '*'
-    and "{m,}" after one element), the literal
+    and "{m,}" after one element; ``runs`` with ``repeat`` changes no kind), the literal
     kernel otherwise.  Every ``NativeEngine`` given the grid must use the same tags."""
     ext = require()
     cls = bool(classes or unicode) and ext.tagset_has_classes(list(tags), bool(classes), bool(unicode), bool(mixed),
-                                                                bool(variants), bool(extended), bool(repeat))
+                                                                bool(variants), bool(extended), bool(repeat), bool(runs))
     return ext.HipGrid(device, doors, wg_per_door, idle_ms, classes=cls)
 
 
@@ -134,7 +165,7 @@ class NativeEngine:
     def __init__(self, kind: str, tags: Sequence[str], device: Optional[int] = None,
                  tile_bytes: int = 16384, max_slots: int = 8192, content_cap: int = 1 << 20, lanes: int = 1,
                  grid=None, door: int = -1, ndoors: int = 1, classes: bool = False, unicode: bool = False,
-                 mixed: bool = False, variants: bool = False, extended: bool = False, repeat: bool = False):
+                 mixed: bool = False, variants: bool = False, extended: bool = False, repeat: bool = False, runs: bool = False):
         ext = require()
         self.kind = kind
         self.name = kind
@@ -145,6 +176,7 @@ class NativeEngine:
         self.variants = bool(variants)
         self.extended = bool(extended)
         self.repeat = bool(repeat)
+        self.runs = bool(runs)
         low = sent_tags(tags, classes, unicode, mixed)
         if kind == "hip":
             if ext.device_count() <= 0:
@@ -155,11 +187,13 @@ class NativeEngine:
             # A class tag set needs a grid made with classes=True (make_grid picks the kind)
             self._e = ext.HipEngine(low, device, tile_bytes, max_slots, content_cap, lanes, grid, door, ndoors,
                                      classes=self.classes, unicode=self.unicode, mixed=self.mixed,
-                                     variants=self.variants, extended=self.extended, repeat=self.repeat)
+                                     variants=self.variants, extended=self.extended, repeat=self.repeat,
+                                     runs=self.runs)
             self.offload = True
         else:
             self._e = ext.CpuEngine(low, classes=self.classes, unicode=self.unicode, mixed=self.mixed,
-                                     variants=self.variants, extended=self.extended, repeat=self.repeat)
+                                     variants=self.variants, extended=self.extended, repeat=self.repeat,
+                                     runs=self.runs)
             self.offload = False
         self.open = self._e.open
         self.feed = self._e.feed

@@ -45,7 +45,8 @@ def native_config(cfg: Dict[str, Any], host: str, port: int, engine: str, device
 
     if not native_tag_ok(tags, classes=bool(rt.native_regex_tags), unicode=bool(rt.native_unicode_tags),
                          mixed=bool(rt.native_mixed_tags), variants=bool(rt.native_variant_tags),
-                         extended=bool(rt.native_extended_tags), repeat=bool(rt.native_repeat_tags)):
+                         extended=bool(rt.native_extended_tags), repeat=bool(rt.native_repeat_tags),
+                         runs=bool(rt.native_run_tags)):
         raise NativeUnsupported(f"thinking_tags {tags!r} need regex semantics: run with --impl python")
     if engine == "auto":
         from ..ops import native
@@ -62,6 +63,7 @@ def native_config(cfg: Dict[str, Any], host: str, port: int, engine: str, device
         "tag_classes": bool(rt.native_regex_tags), "tag_unicode": bool(rt.native_unicode_tags),
         "tag_mixed": bool(rt.native_mixed_tags), "tag_variants": bool(rt.native_variant_tags),
         "tag_extended": bool(rt.native_extended_tags), "tag_repeat": bool(rt.native_repeat_tags),
+        "tag_runs": bool(rt.native_run_tags),
         "aggregator_name": str(agg.aggregator_backend or ""), "prompt_template": str(agg.prompt_template),
         "intermediate_separator": str(agg.intermediate_separator), "query_format": str(agg.query_format),
         "source_label_format": str(agg.source_label_format),

@@ -157,7 +157,7 @@ class ProxyService:
         engine = make_engine(rt.engine, flags.thinking_tags, device=rt.device, classes=rt.native_regex_tags,
                              unicode=rt.native_unicode_tags, mixed=rt.native_mixed_tags,
                              variants=rt.native_variant_tags, extended=rt.native_extended_tags,
-                             repeat=rt.native_repeat_tags)
+                             repeat=rt.native_repeat_tags, runs=rt.native_run_tags)
         ticker = ticker_for(engine)
         sess = ticker.open_session(len(backends), bool(flags.hide_intermediate_think),
                                    not flags.suppress_individual_responses)
@@ -319,7 +319,8 @@ def _stripper(rt: RuntimeConfig, tags: List[str]):
             if native.available():
                 return native.strip_fn(tags, classes=rt.native_regex_tags, unicode=rt.native_unicode_tags,
                                        mixed=rt.native_mixed_tags, variants=rt.native_variant_tags,
-                                       extended=rt.native_extended_tags, repeat=rt.native_repeat_tags)
+                                       extended=rt.native_extended_tags, repeat=rt.native_repeat_tags,
+                                       runs=rt.native_run_tags)
         except Exception:  # noqa: BLE001
             pass
     return lambda text, on: ref.strip_thinking_tags(text, tags, hide_intermediate=on)

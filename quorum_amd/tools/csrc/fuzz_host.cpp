@@ -131,6 +131,40 @@ const ClassSet kClassSets[] = {
      true, true, true, true, true},
 };
 const ClassSet* g_class = nullptr;  // the class tag set of this iteration (null: the default tags)
+constexpr int kClassSetCount = (int)(sizeof(kClassSets) / sizeof(kClassSets[0]));
+// The sets with unbounded repetition run a second time with make_tags' `runs` (the kernels' rule for a
+// run longer than the rows, qmx_text.h WALK_RUNS): the host engines' bytes must not depend on it.
+int repeat_set(int k) {  // the k-th set with `repeat`, counted round
+  int nrep = 0;
+  for (const ClassSet& c : kClassSets) nrep += c.repeat;
+  k %= nrep;
+  for (int i = 0; i < kClassSetCount; ++i)
+    if (kClassSets[i].repeat && k-- == 0) return i;
+  return 0;
+}
+int repeat_sets() {
+  int nrep = 0;
+  for (const ClassSet& c : kClassSets) nrep += c.repeat;
+  return nrep;
+}
+
+// The kernels' candidate rule on the host (device_token_at) against the exact walk (token_at): at
+// every '<' of a text the rule either leaves the candidate to the host (suspect) or answers the exact
+// walk's token and byte length, with the streaming and with the strip tables.
+bool device_rule_holds(const Tags& tags, const std::string& text) {
+  const uint8_t* x = (const uint8_t*)text.data();
+  const int n = (int)text.size();
+  for (int strip = 0; strip < 2; ++strip)
+    for (int p = 0; p < n; ++p) {
+      if (x[p] != '<') continue;
+      int tok = 0, len = 0, want_len = 0;
+      const int r = device_token_at(tags.kind, x, n, p, tags.ts, tags.tc, strip != 0, &tok, &len);
+      if (r == CC_SUSPECT) continue;
+      const int want = token_at(tags.kind, x, n, p, tags.ts, tags.tc, strip != 0, &want_len);
+      if (tok != want || (want != 0 && len != want_len)) return false;
+    }
+  return true;
+}
 
 std::string rand_content() {
   std::string s;
@@ -255,10 +289,10 @@ bool malformed_tags_hold() {
   std::vector<std::string> tags;
   const int n = 1 + R(3);
   for (int i = 0; i < n; ++i) tags.push_back(rand_tag());
-  const bool unicode = R(2), mixed = R(2), variants = R(4) != 0, extended = R(3) != 0, repeat = R(2) != 0;
+  const bool unicode = R(2), mixed = R(2), variants = R(4) != 0, extended = R(3) != 0, repeat = R(2) != 0, runs = R(2) != 0;
   try {
-    const Tags t = make_tags(tags, true, unicode, mixed, variants, extended, repeat);
-    const auto rows = tagset_rows(tags, true, unicode, mixed, variants, extended, repeat);
+    const Tags t = make_tags(tags, true, unicode, mixed, variants, extended, repeat, runs);
+    const auto rows = tagset_rows(tags, true, unicode, mixed, variants, extended, repeat, runs);
     if ((int)rows.size() != t.ts.n || t.ts.n > kMaxTags) return false;
     std::string text = "<" + tags[0] + "></" + tags[0] + "><";
     for (const auto& r : rows) text += "<" + r.first + ">x</" + r.first + ">";
@@ -307,12 +341,15 @@ int main(int argc, char** argv) {
   int fails = 0;
   for (int it = 0; it < iters; ++it) {
     // every other iteration: one of the class tag sets
-    g_class = it % 2 ? &kClassSets[(it / 2) % (int)(sizeof(kClassSets) / sizeof(kClassSets[0]))] : nullptr;
+    // (then the sets with unbounded repetition once more, with `runs`)
+    const int pick = (it / 2) % (kClassSetCount + repeat_sets());
+    const bool runs = it % 2 && pick >= kClassSetCount;
+    g_class = it % 2 ? &kClassSets[runs ? repeat_set(pick - kClassSetCount) : pick] : nullptr;
     const Tags tags = make_tags(g_class ? g_class->tags : default_tags,
                                 g_class != nullptr && (!g_class->unicode || g_class->mixed),
                                 g_class != nullptr && g_class->unicode, g_class != nullptr && g_class->mixed,
                                 g_class != nullptr && g_class->variants, g_class != nullptr && g_class->extended,
-                                g_class != nullptr && g_class->repeat);
+                                g_class != nullptr && g_class->repeat, runs);
     int ns = 1 + R(4);
     std::vector<std::string> bodies;
     std::vector<bool> filt;
@@ -331,6 +368,16 @@ int main(int argc, char** argv) {
     }
     if (!malformed_tags_hold()) {
       if (++fails <= 3) fprintf(stderr, "malformed tags: rows and tables disagree (iteration %d)\n", it);
+    }
+    if (runs) {
+      const std::string text = rand_content() + rand_content() + rand_content();
+      if (!device_rule_holds(tags, text) && ++fails <= 3)
+        fprintf(stderr, "device candidate rule differs from the exact walk (iteration %d): %s\n", it, text.c_str());
+      // the host engines' bytes do not depend on `runs`
+      const Tags plain = make_tags(g_class->tags, !g_class->unicode || g_class->mixed, g_class->unicode, g_class->mixed,
+                                   g_class->variants, g_class->extended, g_class->repeat);
+      if (!same(whole, run_engine(plain, bodies, filt, false)) && ++fails <= 3)
+        fprintf(stderr, "runs changed the host engine's output (iteration %d)\n", it);
     }
     // strip_final: stripping a stripped text (no tags left in it) only re-strips whitespace
     std::string t = rand_content() + rand_content();

@@ -325,6 +325,15 @@ class RuntimeConfig:
                longest open-ended; a longer run is decided on the host, and a match is at most 61
                bytes.  A repeat after a group, after a non-ASCII literal and the lazy forms are still
                refused.  Off (the default): such a tag needs the python engine
+    native_run_tags: with native_regex_tags, native_variant_tags, native_extended_tags and
+               native_repeat_tags all on (refused otherwise), the GPU engine also decides a run longer
+               than the rows — "<step12345>", "<think      >", "<v12345.678901>" — where every copy is
+               an ASCII character other than '<' and '>': the stream stays on the GPU.  A non-ASCII
+               character in a run ("<step12٣45>") and a '<' or '>' the repeated class accepts
+               ("n[^0-9x]+x" with "<n<x>") are still decided on the host, as everything the keys above
+               leave to it.  What runs natively, the rows and every output byte are the same; a match
+               is still at most 61 bytes.  Off (the default): a run of more than 4 copies beyond the
+               minimum moves its stream to the host path
     """
 
     engine: str = "auto"
@@ -354,6 +363,7 @@ class RuntimeConfig:
     native_variant_tags: bool = False
     native_extended_tags: bool = False
     native_repeat_tags: bool = False
+    native_run_tags: bool = False
 
     def __post_init__(self):
         if not isinstance(self.native_regex_tags, bool):
@@ -380,6 +390,12 @@ class RuntimeConfig:
                                             and self.native_extended_tags):
             raise ValueError("runtime.native_repeat_tags needs runtime.native_regex_tags, "
                              "runtime.native_variant_tags and runtime.native_extended_tags all true")
+        if not isinstance(self.native_run_tags, bool):
+            raise ValueError(f"runtime.native_run_tags must be true or false, got {self.native_run_tags!r}")
+        if self.native_run_tags and not (self.native_regex_tags and self.native_variant_tags
+                                         and self.native_extended_tags and self.native_repeat_tags):
+            raise ValueError("runtime.native_run_tags needs runtime.native_regex_tags, runtime.native_variant_tags, "
+                             "runtime.native_extended_tags and runtime.native_repeat_tags all true")
 
     @classmethod
     def from_config(cls, cfg: Dict[str, Any]) -> "RuntimeConfig":

@@ -87,6 +87,9 @@ def main():
                     help="with --classes --variants --extended: '+', '*' and '{m,}' after one element "
                          "(runtime.native_repeat_tags), e.g. --tags 'think,step\\d+' --body-tag step12 (decided by the rows, "
                          "on the GPU) or --body-tag step12345 (a run longer than the rows: every stream goes to the host)")
+    ap.add_argument("--runs", action="store_true",
+                    help="with --repeat: the GPU decides a run longer than the rows (runtime.native_run_tags), e.g. "
+                         "--tags 'think,step\\d+' --body-tag step12345 stays on the GPU")
     ap.add_argument("--body-tag", default="think",
                     help="mock shape: the think block's tag as the upstream writes it, e.g. réflexion or RÉFLEXION")
     args = ap.parse_args()
@@ -104,7 +107,7 @@ def main():
         # (so does a pair tag set: --unicode and a cased non-ASCII character in a tag)
         grid = ext.HipGrid(0, args.grid, 8, classes=(args.classes or args.unicode)
                            and ext.tagset_has_classes(tags, args.classes, args.unicode, args.mixed, args.variants,
-                                                      args.extended, args.repeat))
+                                                      args.extended, args.repeat, args.runs))
     combos = {"ft": (True, True), "f": (True, False), "t": (False, True)}
     for filt, emit in [combos[c] for c in args.combos.split(",")]:
         for n in [int(x) for x in args.slots.split(",")]:
@@ -121,6 +124,8 @@ def main():
                 kw["extended"] = True
             if args.repeat:
                 kw["repeat"] = True
+            if args.runs:
+                kw["runs"] = True
             eng = NativeEngine(args.engine, tags, device=0, max_slots=4096, content_cap=1 << 16, **kw)
             walls = []
             evs = [e + b"\n\n" for e in body.split(b"\n\n") if e]
